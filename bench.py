@@ -12,9 +12,20 @@ dataset (planning + kernels + delivery of the complete nav result to the host of
 the whole hot path, not just the kernel.  Weak scaling: every rank holds its own 256x256-scan shard
 (65536 frames, 8 GiB); the nav grid of the job is N x that.
 
-Rank 0 prints ONE JSON line.  `value` / `roofline` / `cpu_baseline` are the C2 figures the contract
-asks for; `roofline` also carries the strict float32-instruction leg of C2 as flat scalars (`f32_instr_*`).
-The same line carries, as extra keys (all configs, both timing modes):
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times
+the K steps, writes the outputs of the last timed step if asked (`--dump-outputs`) and prints the line --
+`value` (frames/s), `ms_per_step` (one timed step, max over ranks), `roofline` (the dominant kernel, from
+HIP events inside the same timed steps), `per_rank`, `result_via`.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0's copy: the complete
+nav result) as DIR/<result name>.npy: float32 / float64 arrays as they are, complex ones as <name>_real /
+<name>_imag, integer ones as float64; more than 64 MB in all -> a fixed, seeded sample of the rows of each
+array (last axis kept).  The inputs are seeded: the same arguments give the same inputs in every run.
+
+`--full` adds everything else around the same headline: the check of the first step's result against
+float64 NumPy (and, at N = 1, the oracle), `cpu_baseline`, the strict float32-instruction leg of C2 (flat
+scalars `roofline.f32_instr_*` and `f32_instruction`), and, as extra keys (all configs,
+both timing modes; `--no-extras` / `--no-cpu-baseline` leave parts out):
 
   N = 1:  "configs": {"c3": ..., "c4": ..., "c5": ...}   whole job + dominant kernel + roofline + cpu_baseline each
           (C5's roofline is priced against HBM; `mfma_algorithmic_frac` / `mfma_issued_frac` ride beside it)
@@ -32,7 +43,7 @@ The same line carries, as extra keys (all configs, both timing mod
                        over the N ranks (strong scaling).
 
 `--config c3|c4|c5` makes that config the measured one (`value` then is ITS frames/s; used by
-scripts/profile_round.sh for per-config rocprofv3 passes); `--no-extras` skips the extra keys;
+scripts/profile_round.sh for per-config rocprofv3 passes);
 `--result-via shm|rccl` picks the delivery of the nav results across ranks (default: the executor's choice).
 
 `roofline.achieved` = algorithmic bytes (or flops) per launch / average launch duration from HIP
@@ -367,12 +378,13 @@ def load_tail(name, kname, frames_per_launch):
     return None, None
 
 
-def measure(wl, steps, warmup, barrier, hip, n_check=32, traffic_name=None):
-    """W untimed + K timed steps of a workload; returns whole-job and dominant-kernel figures."""
+def measure(wl, steps, warmup, barrier, hip, n_check=32, traffic_name=None, check=True, keep_last=False):
+    """W untimed + K timed steps of a workload; returns whole-job and dominant-kernel figures
+    (check: the first step's result against float64 NumPy; keep_last: the last timed step's result as 'last')."""
     import re
     cfg = wl.cfg
     res = wl.step()
-    err = wl.check(res, n_check=n_check)
+    err = wl.check(res, n_check=n_check) if check else None
     del res
     # The oracle / float64 checks above leave the GPU idle for ~1 s and its clocks (sclk / mclk DPM)
     # come back over the next ~20 ms of load -- longer than a handful of C2 steps
@@ -394,9 +406,13 @@ def measure(wl, steps, warmup, barrier, hip, n_check=32, traffic_name=None):
     barrier()
     t0 = time.perf_counter()
     marks = []
+    last = None
     try:
-        for _ in range(steps):
-            wl.step()
+        for i in range(steps):
+            if keep_last and i == steps - 1:
+                last = wl.step()
+            else:
+                wl.step()
             marks.append(time.perf_counter())
         barrier()
         elapsed = time.perf_counter() - t0
@@ -466,7 +482,7 @@ def measure(wl, steps, warmup, barrier, hip, n_check=32, traffic_name=None):
     return dict(elapsed=elapsed, ms_per_step=elapsed / steps * 1e3, roofline=roof,
                 ms_per_step_median=float(np.median(step_ms)) if step_ms else None,
                 kernel_ms_per_step=float(np.sum(kms)) / steps, check_rel_err=err,
-                preheat_steps=preheat)
+                preheat_steps=preheat, last=last)
 
 
 def host_streamed(ctx, torch, hip, gib=2):
@@ -891,6 +907,49 @@ def mib_decode(torch, hip, n=16384, reps=10):
                          "traffic": traffic, "traffic_source": source}}
 
 
+# --------------------------------------------------------------------------------------------------
+# outputs of the timed path (--dump-outputs)
+# --------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def result_arrays(res):
+    """[(name, float32 / float64 ndarray)] of what a caller of the timed step receives: the buffers of a
+    UDF result, or the results and raw_results of an analysis; complex -> <name>_real / <name>_imag,
+    integer / bool -> float64"""
+    if hasattr(res, 'items'):
+        items = [(k, v.data) for k, v in res.items()]
+    else:
+        items = [(r.key, r.raw_data) for r in res]
+        if getattr(res, 'raw_results', None) is not None:
+            items.append(('raw_results', res.raw_results))
+    out = []
+    for name, a in items:
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            f = np.float64 if a.dtype == np.complex128 else np.float32
+            out += [(f'{name}_real', a.real.astype(f)), (f'{name}_imag', a.imag.astype(f))]
+        elif a.dtype in (np.float32, np.float64):
+            out.append((name, np.array(a)))
+        else:
+            out.append((name, a.astype(np.float64)))
+    return out
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """out_dir/<name>.npy for every array; above `limit` bytes in all, every array is cut down to a fixed,
+    seeded sample of its rows (the last axis kept whole), in proportion to its size"""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for _, a in arrays)
+    for name, a in arrays:
+        if total > limit and a.size > 1:
+            rows = a.reshape((-1, a.shape[-1])) if a.ndim > 1 else a.reshape((-1, 1))
+            keep = max(1, rows.shape[0] * limit // total)
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+            a = rows[idx] if a.ndim > 1 else rows[idx, 0]
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-exec this command line under
     torch.distributed.run (N ranks on this node, rendezvous on 127.0.0.1 at a free port); the ranks
@@ -918,14 +977,22 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='c2', choices=sorted(CONFIGS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help="besides the headline: result checks, CPU baselines, the float32-instruction leg of C2 "
+                         "and the extra keys (other configs, timing modes, multi-rank paths)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help="with --full: no cpu_baseline")
+    ap.add_argument('--no-extras', action='store_true', help="with --full: no extra keys")
     ap.add_argument('--result-via', default='auto', choices=['auto', 'shm', 'rccl'],
                     help="delivery of the nav results across ranks: the node-shared page-locked host segment (shm) or "
                          "the RCCL all-gather over xGMI (rccl); auto = the executor's default (shm on one node).  At "
                          "--gpus 1 a value other than auto forces the multi-rank delivery path with a world of one "
                          "(LTMI_FORCE_COLLECTIVES=1): the N = 1 anchor of that path")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.result_via != 'auto':
         os.environ['LTMI_RESULT_VIA'] = args.result_via
         if args.gpus == 1:
@@ -943,10 +1010,10 @@ def main():
     # test hooks (one-GPU box: several gloo ranks on one device exercise the N>1 flow end to end)
     device_id = int(os.environ.get('LTMI_BENCH_DEVICE', local_rank))
     backend = os.environ.get('LTMI_BENCH_BACKEND', 'nccl')
-    extras = not args.no_extras and os.environ.get('LTMI_BENCH_EXTRAS', '1') != '0' \
+    extras = args.full and not args.no_extras and os.environ.get('LTMI_BENCH_EXTRAS', '1') != '0' \
         and args.config == 'c2'
     cpu_base, cpu_all = None, {}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # rank 0 at N=1 only, and BEFORE the HIP runtime is initialised (fork-safe): the measured config, and --
         # with the extras -- every other config whose line rides along (the CPU path beside each)
         names = [args.config if args.config in _CPU_SAMPLES else 'c2']
@@ -1005,12 +1072,16 @@ def main():
     fpr = int(fpr) if fpr else None
     wl = Workload(args.config, ctx, torch, rank, world, sharded=use_dist, frames_per_rank=fpr)
     wl.use_oracle = cpu_base is not None           # N = 1: the oracle also checks 32 result rows
-    m = measure(wl, args.steps, args.warmup, barrier, hip)
+    m = measure(wl, args.steps, args.warmup, barrier, hip, check=args.full,
+                keep_last=args.dump_outputs is not None)
     result_via = getattr(ctx.executor, 'last_result_via', 'local')
     elapsed_max = max_over_ranks(m['elapsed'])
     per_rank = gather_list({"rank": rank, "ms_per_step": m['ms_per_step'],
                             "kernel_ms_per_step": m['kernel_ms_per_step'],
                             "kernel_avg_launch_ms": m['roofline']['avg_launch_ms']})
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(result_arrays(m['last']), args.dump_outputs)
+    m['last'] = None
     n_frames, n_px, itemsize = wl.n_local, wl.n_px, wl.itemsize
     total_frames = n_frames * world * args.steps
     value = total_frames / elapsed_max
@@ -1018,7 +1089,7 @@ def main():
     # the same K steps on the float32 matrix instruction only (v_mfma_f32_16x16x4_f32: the strict reading
     # of "MFMA f32" in the north star), same handle, same plan -- every rank takes this path
     f32_leg = None
-    if args.config.startswith('c2'):
+    if args.full and args.config.startswith('c2'):
         os.environ['LTMI_DENSE_F32_INSTR'] = '1'
         try:
             mf = measure(wl, args.steps, args.warmup, barrier, hip, n_check=8, traffic_name='c2_f32')

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+CMD="python $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline"
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/${tag}_stats -o bench -- $CMD > $out/${tag}_stats.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/${tag}_fetch -o bench -- $CMD > $out/${tag}_fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $out/${tag}_write -o bench -- $CMD > $out/${tag}_write.log 2>&1

@@ -10,7 +10,7 @@ out=$R/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for c in $cfgs; do
-  CMD="python $R/bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-extras"
+  CMD="python $R/bench.py --config $c --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras"
   timeout 600 rocprofv3 --kernel-trace --stats -d $out/${c}_stats -o bench -- $CMD > $out/${c}_stats.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/${c}_fetch -o bench -- $CMD > $out/${c}_fetch.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $out/${c}_write -o bench -- $CMD > $out/${c}_write.log 2>&1

@@ -1838,10 +1838,10 @@ def test_bench_contract_with_two_ranks_on_one_gpu(launcher):
     if launcher == 'torchrun':
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2',
                '--master-addr', '127.0.0.1', '--master-port', str(port),
-               os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1']
+               os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full']
     else:
         cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3',
-               '--warmup', '1']
+               '--warmup', '1', '--full']
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1901,7 +1901,8 @@ def test_bench_contract_with_eight_ranks_on_one_gpu():
                LTMI_BENCH_FRAMES_PER_RANK='8192', LTMI_BENCH_PREHEAT='4')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '6', '--warmup', '2']
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '6', '--warmup', '2',
+           '--full']
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1923,6 +1924,46 @@ def test_bench_contract_with_eight_ranks_on_one_gpu():
     assert 0 < d['roofline']['f32_instr_kernel_frac'] < 1 and d['roofline']['f32_instr_ms_per_step'] > 0
     assert d['roofline']['f32_instr_rel_err'] < 1e-5 and len(d['config']['arithmetic_detail']) < 240
     assert not [f for f in os.listdir('/dev/shm') if f.startswith(f'ltmi_{os.getuid()}_')]
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (4096 frames through the test hook): the
+    headline line only -- no checks, baselines or extra keys -- and DIR/intensity.npy is the result of the last
+    timed step: the 16 masks applied to the seeded frames, against float64 NumPy."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, LTMI_BENCH_FRAMES_PER_RANK='4096', LTMI_BENCH_PREHEAT='2')
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
+        env.pop(k, None)
+    out_dir = tmp_path / 'out'
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2',
+           '--dump-outputs', str(out_dir)]
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 4 and d['warmup'] == 2 and d['n_gpus'] == 1
+    assert d['metric'].startswith('frames/sec') and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['ms_per_step'] > 0
+    assert abs(d['value'] * d['ms_per_step'] / 1e3 - 4096) < 1e-6 * 4096
+    assert d['roofline']['bound'] == 'hbm' and d['roofline']['launches_timed'] >= 4
+    assert d['f32_instruction'] is None and d['result_check_rel_err_vs_float64'] is None
+    for key in ('cpu_baseline', 'configs', 'host_streamed', 'small_tiles', 'live_feed', 'mib_decode',
+                'crystallinity', 'second_runs', 'delivery_anchor_n1', 'rccl_path', 'strong_c3'):
+        assert key not in d, key
+    assert sorted(os.listdir(out_dir)) == ['intensity.npy']
+    got = np.load(out_dir / 'intensity.npy')
+    assert got.dtype == np.float32 and got.shape == (16, 256, 16)
+    frames = bench.device_frames(torch, 4096, (256, 256), 'uint16', 1 + 17 * len('c2'))
+    masks = np.random.default_rng(2).random((16, 256 * 256)).astype(np.float64)
+    idx = [0, 1, 777, 2048, 4095]
+    ref = frames[idx].cpu().numpy().view(np.uint16).astype(np.float64) @ masks.T
+    assert _close(got.reshape((-1, 16))[idx], ref, F32_TOL)
 
 
 # ---- caches and launch-ahead state: staleness and concurrency (round-4 review) ---------------------------------
