@@ -232,6 +232,24 @@ int ltmi_sum_frames(int device, const void *tile, int tile_dtype, int64_t n_fram
  * (result_type(input, float32), udf/sumsigudf.py:23) */
 int ltmi_sum_sig(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
                  int64_t ld_tile, void *out, int out_dtype, int accumulate, void *stream);
+/* StdDevUDF.process_tile: fold the n_frames frames of `tile` into running per-pixel moments
+ * (src/libertem/udf/stddev.py:103-168 `process_tile`, :425-451 `StdDevUDF.process_tile`):
+ *   sum[p]    = sum of the frames,  varsum[p] = sum over frames of |x - mean|^2,
+ * both over the n_prev frames they already hold plus the tile's; n_prev == 0 overwrites them.
+ * The tile's moments are computed per slab of frames in float64 about a shift (the slab's first
+ * frame), the slabs and the running buffers are merged in a fixed order with the reference's
+ * update (stddev.py:11-63): varsum += varsum_tile + n_tile |delta| |delta'| -- no atomics, the
+ * results are bitwise repeatable.
+ *   tile dtypes: uint8, int8, uint16, int16, uint32, int32, float32, float64, complex64, complex128;
+ *   sum_dtype: float32 / float64 for real tiles, complex64 / complex128 for complex tiles;
+ *   varsum_dtype: float32 / float64 (|x - mean|^2 of complex pixels).
+ * Tile pixel p is element (p / cols) * ld_out + p % cols of `sum` and `varsum` (the strided
+ * sub-rectangle of a partial-width sig slice; cols = ld_out = n_px: contiguous); n_px % cols == 0.
+ * `workspace`: device scratch of ltmi_moments_workspace(n_frames, n_px, tile_dtype) bytes. */
+int64_t ltmi_moments_workspace(int64_t n_frames, int64_t n_px, int tile_dtype);
+int ltmi_moments_frames(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
+                        int64_t ld_tile, int64_t n_prev, void *sum, int sum_dtype, void *varsum,
+                        int varsum_dtype, int64_t cols, int64_t ld_out, void *workspace, void *stream);
 
 /* merge for sig-kind buffers: dest[i] += src[i]          (src/libertem/udf/sum.py:50-52);
  * every dtype of enum ltmi_dtype, integers wrap around like NumPy's `+=` */

@@ -9,8 +9,9 @@ from .com import COMAnalysis
 from .radialfourier import RadialFourierAnalysis
 from .fft import ApplyFFTMask, SumfftAnalysis
 from .raw import PickFrameAnalysis, PickFFTFrameAnalysis
+from .sd import SDAnalysis
 
 __all__ = ['PickFrameAnalysis', 'PickFFTFrameAnalysis', 'Analysis', 'AnalysisResult', 'AnalysisResultSet', 'MasksAnalysis',
            'BaseMasksAnalysis', 'SingleMaskAnalysis', 'DiskMaskAnalysis', 'RingMaskAnalysis',
            'PointMaskAnalysis', 'SumAnalysis', 'SumSigAnalysis', 'COMAnalysis',
-           'RadialFourierAnalysis', 'ApplyFFTMask', 'SumfftAnalysis']
+           'RadialFourierAnalysis', 'ApplyFFTMask', 'SumfftAnalysis', 'SDAnalysis']

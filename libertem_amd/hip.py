@@ -32,6 +32,7 @@ EXPORTS = (
     'ltmi_masks_set_sparse_origin', 'ltmi_masks_set_dense_origin', 'ltmi_masks_create_csr_gather',
     'ltmi_masks_nonfinite_frames',
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
+    'ltmi_moments_workspace', 'ltmi_moments_frames',
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_masks_set_tuning',
@@ -252,6 +253,9 @@ def lib():
         L.ltmi_sum_frames_workspace.restype = i64
         L.ltmi_sum_frames.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, i32, vp, vp]
         L.ltmi_sum_sig.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, i32, vp]
+        L.ltmi_moments_workspace.argtypes = [i64, i64, i32]
+        L.ltmi_moments_workspace.restype = i64
+        L.ltmi_moments_frames.argtypes = [i32, vp, i32, i64, i64, i64, i64, vp, i32, vp, i32, i64, i64, vp, vp]
         L.ltmi_axpy.argtypes = [i32, vp, vp, i32, i64, vp]
         L.ltmi_add2d.argtypes = [i32, vp, i64, vp, i64, i32, i64, i64, i32, vp]
         L.ltmi_gather_rows.argtypes = [i32, vp, i64, vp, i64, i64, vp, vp]
@@ -548,6 +552,23 @@ def sum_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, o
         int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), n_frames, n_px, ld_tile,
         ctypes.c_void_p(out_ptr), dtype_code(out_dtype), 1 if accumulate else 0,
         ctypes.c_void_p(workspace_ptr), _stream_ptr(stream)), 'ltmi_sum_frames')
+
+
+def moments_workspace(n_frames, n_px, tile_dtype):
+    return int(lib().ltmi_moments_workspace(n_frames, n_px, dtype_code(tile_dtype)))
+
+
+def moments_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, n_prev, sum_ptr, sum_dtype,
+                   varsum_ptr, varsum_dtype, workspace_ptr, cols=None, ld_out=None, stream=None):
+    """fold a tile into running per-pixel (sum, varsum) of `n_prev` frames (StdDevUDF); pixel p of the
+    tile is element (p // cols) * ld_out + p % cols of the outputs (default: contiguous)"""
+    cols = n_px if cols is None else cols
+    ld_out = cols if ld_out is None else ld_out
+    check(lib().ltmi_moments_frames(
+        int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), n_frames, n_px, ld_tile,
+        int(n_prev), ctypes.c_void_p(sum_ptr), dtype_code(sum_dtype), ctypes.c_void_p(varsum_ptr),
+        dtype_code(varsum_dtype), int(cols), int(ld_out), ctypes.c_void_p(workspace_ptr),
+        _stream_ptr(stream)), 'ltmi_moments_frames')
 
 
 def sum_sig(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, out_dtype,

@@ -296,6 +296,11 @@ class MIBDataSet(MemoryDataSet):
                 self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
                 num_partitions=self._num_partitions_arg, shard=self._shard_arg)
         self._sync_offset = so
+        # scan positions that hold a frame of the series (global positions; frame g sits at g - so): the rest are
+        # the zero frames decoded above, which UDFs with `VALID_FRAMES_ONLY` are not handed
+        lo = min(n_nav, max(0, -so))
+        hi = max(lo, min(n_nav, self._image_count - so))
+        self._valid_frames = None if (lo, hi) == (0, n_nav) else (lo, hi)
         self._meta = DataSetMeta(shape=self._shape, raw_dtype=np.dtype(first['dtype']),
                                  sync_offset=so, image_count=self._image_count)
         return MemoryDataSet.initialize(self, executor)

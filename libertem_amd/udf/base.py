@@ -827,6 +827,37 @@ class UDFTask:
         return f"<UDFTask {self._udf_classes!r}>"
 
 
+def _valid_compressed_range(partition, roi):
+    """[first, last) of the (ROI-compressed) nav positions that hold a frame of the dataset, if a sync_offset left
+    positions without one (`_valid_frames` of the dataset, global frame indices); None: every position has one"""
+    valid = getattr(getattr(partition, '_ds', None), '_valid_frames', None)
+    if valid is None:
+        return None
+    lo, hi = int(valid[0]), int(valid[1])
+    if roi is not None:
+        r = np.asarray(roi, dtype=bool).reshape(-1)
+        lo, hi = int(np.count_nonzero(r[:lo])), int(np.count_nonzero(r[:hi]))
+    return lo, hi
+
+
+def _trim_tile(tile, valid):
+    """the frames of `tile` inside the nav range `valid`, as a tile (the same one if all are); None: no frame"""
+    from libertem_amd.io.dataset.base import DataTile
+    t0 = int(tile.tile_slice.origin[0])
+    n = int(tile.tile_slice.shape[0])
+    a, b = max(t0, valid[0]), min(t0 + n, valid[1])
+    if a >= b:
+        return None
+    if (a, b) == (t0, t0 + n):
+        return tile
+    data = tile.data
+    data = data.rows(a - t0, b - t0) if hasattr(data, 'rows') else data[a - t0:b - t0]
+    sl = tile.tile_slice
+    new_slice = Slice(origin=(a,) + tuple(sl.origin[1:]),
+                      shape=Shape((b - a,) + tuple(sl.shape)[1:], sig_dims=sl.shape.sig_dims))
+    return DataTile(data, new_slice, tile.scheme_idx)
+
+
 class UDFPartRunner:
     """Per-partition driver on the worker (udf/base.py:2094-2335)."""
 
@@ -999,9 +1030,18 @@ class UDFPartRunner:
                          and udf.results.get_buffer(k).kind == 'nav']
                 if names:
                     sinkable.append((i, udf, names))
+        # positions a sync_offset left without a frame, for UDFs that must not see the zero frames the device path
+        # delivers there (`VALID_FRAMES_ONLY`; host tiles skip them already)
+        valid = _valid_compressed_range(partition, params.roi) \
+            if any(getattr(u, 'VALID_FRAMES_ONLY', False) for u in self._udfs) else None
         for tile in tiles:
             for udf, method in zip(self._udfs, methods):
                 try:
+                    if valid is not None and getattr(udf, 'VALID_FRAMES_ONLY', False):
+                        vt = _trim_tile(tile, valid)
+                        if vt is not None:
+                            self._run_tile(udf, method, partition, vt)
+                        continue
                     self._run_tile(udf, method, partition, tile)
                 except AttributeError as e:
                     # tiles are plain arrays: what DataTile objects once carried is on `self.meta`
