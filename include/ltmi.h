@@ -250,6 +250,29 @@ int64_t ltmi_moments_workspace(int64_t n_frames, int64_t n_px, int tile_dtype);
 int ltmi_moments_frames(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
                         int64_t ld_tile, int64_t n_prev, void *sum, int sum_dtype, void *varsum,
                         int varsum_dtype, int64_t cols, int64_t ld_out, void *workspace, void *stream);
+/* FEMUDF.process_frame: out[f] = np.std(frame_f[mask == 1])     (src/libertem/udf/FEM.py:65-66)
+ * for the n_frames whole frames of `tile` (frame f at element f * ld_tile, pixel (r, x) at r * width + x;
+ * complex pixels count as one element).  The ring is `spans`: device memory of n_spans int32 triples
+ * (row, x0, x1), x0 < x1 <= width, row inside the frame, built on the host from the boolean mask
+ * (FEM.py:44-63); n_ring = sum of x1 - x0.  Per frame float64 sums about the first ring pixel, reduced
+ * in one workgroup in a fixed order (no atomics: bitwise repeatable); result sqrt(M2 / n) as float32,
+ * ddof = 0, |x - mean|^2 for complex pixels.  An empty ring, or a NaN / inf pixel in it, gives NaN.
+ *   tile dtypes: uint8, int8, uint16, int16, uint32, int32, float32, float64, complex64, complex128. */
+int ltmi_ring_moments(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t width,
+                      int64_t ld_tile, const void *spans, int n_spans, int64_t n_ring, void *out,
+                      void *stream);
+/* LogsumUDF.process_frame: out[p] += sum_f log(frame_f[p] - min(frame_f) + 1)
+ * (src/libertem/udf/logsum.py:54-59) for the n_frames whole frames (n_px pixels) of `tile`.  Each term is
+ * rounded in result_type(float32, tile dtype) (float for <= 16-bit integers and float32, double for
+ * 32-bit integers and float64), the min propagates NaN (np.min); the terms are summed in float64 per
+ * slab of frames and merged in a fixed order into the float32 `out` (no atomics: bitwise repeatable).
+ *   tile dtypes: uint8, int8, uint16, int16, uint32, int32, float32, float64 (complex: LTMI_E_DTYPE).
+ * Tile pixel p is element (p / cols) * ld_out + p % cols of `out`; n_px % cols == 0.
+ * `workspace`: device scratch of ltmi_logsum_workspace(n_frames, n_px, tile_dtype) bytes. */
+int64_t ltmi_logsum_workspace(int64_t n_frames, int64_t n_px, int tile_dtype);
+int ltmi_logsum_frames(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
+                       int64_t ld_tile, void *out, int64_t cols, int64_t ld_out, void *workspace,
+                       void *stream);
 
 /* merge for sig-kind buffers: dest[i] += src[i]          (src/libertem/udf/sum.py:50-52);
  * every dtype of enum ltmi_dtype, integers wrap around like NumPy's `+=` */

@@ -10,8 +10,9 @@ from .radialfourier import RadialFourierAnalysis
 from .fft import ApplyFFTMask, SumfftAnalysis
 from .raw import PickFrameAnalysis, PickFFTFrameAnalysis
 from .sd import SDAnalysis
+from .fem import FEMAnalysis
 
 __all__ = ['PickFrameAnalysis', 'PickFFTFrameAnalysis', 'Analysis', 'AnalysisResult', 'AnalysisResultSet', 'MasksAnalysis',
            'BaseMasksAnalysis', 'SingleMaskAnalysis', 'DiskMaskAnalysis', 'RingMaskAnalysis',
            'PointMaskAnalysis', 'SumAnalysis', 'SumSigAnalysis', 'COMAnalysis',
-           'RadialFourierAnalysis', 'ApplyFFTMask', 'SumfftAnalysis', 'SDAnalysis']
+           'RadialFourierAnalysis', 'ApplyFFTMask', 'SumfftAnalysis', 'SDAnalysis', 'FEMAnalysis']

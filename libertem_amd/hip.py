@@ -32,7 +32,8 @@ EXPORTS = (
     'ltmi_masks_set_sparse_origin', 'ltmi_masks_set_dense_origin', 'ltmi_masks_create_csr_gather',
     'ltmi_masks_nonfinite_frames',
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
-    'ltmi_moments_workspace', 'ltmi_moments_frames',
+    'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
+    'ltmi_logsum_frames',
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_masks_set_tuning',
@@ -256,6 +257,10 @@ def lib():
         L.ltmi_moments_workspace.argtypes = [i64, i64, i32]
         L.ltmi_moments_workspace.restype = i64
         L.ltmi_moments_frames.argtypes = [i32, vp, i32, i64, i64, i64, i64, vp, i32, vp, i32, i64, i64, vp, vp]
+        L.ltmi_ring_moments.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, i64, vp, vp]
+        L.ltmi_logsum_workspace.argtypes = [i64, i64, i32]
+        L.ltmi_logsum_workspace.restype = i64
+        L.ltmi_logsum_frames.argtypes = [i32, vp, i32, i64, i64, i64, vp, i64, i64, vp, vp]
         L.ltmi_axpy.argtypes = [i32, vp, vp, i32, i64, vp]
         L.ltmi_add2d.argtypes = [i32, vp, i64, vp, i64, i32, i64, i64, i32, vp]
         L.ltmi_gather_rows.argtypes = [i32, vp, i64, vp, i64, i64, vp, vp]
@@ -569,6 +574,32 @@ def moments_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, n_prev
         int(n_prev), ctypes.c_void_p(sum_ptr), dtype_code(sum_dtype), ctypes.c_void_p(varsum_ptr),
         dtype_code(varsum_dtype), int(cols), int(ld_out), ctypes.c_void_p(workspace_ptr),
         _stream_ptr(stream)), 'ltmi_moments_frames')
+
+
+def ring_moments(device, tile_ptr, tile_dtype, n_frames, width, ld_tile, spans_ptr, n_spans, n_ring,
+                 out_ptr, stream=None):
+    """out[f] (float32) = std of the ring pixels of frame f (FEMUDF); `spans_ptr`: device int32 triples
+    (row, x0, x1) of the ring, n_ring pixels in all"""
+    check(lib().ltmi_ring_moments(
+        int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), int(n_frames), int(width),
+        int(ld_tile), ctypes.c_void_p(spans_ptr), int(n_spans), int(n_ring), ctypes.c_void_p(out_ptr),
+        _stream_ptr(stream)), 'ltmi_ring_moments')
+
+
+def logsum_workspace(n_frames, n_px, tile_dtype):
+    return int(lib().ltmi_logsum_workspace(n_frames, n_px, dtype_code(tile_dtype)))
+
+
+def logsum_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, workspace_ptr,
+                  cols=None, ld_out=None, stream=None):
+    """out[p] (float32) += sum over the tile's frames of log(x - min(frame) + 1) (LogsumUDF); pixel p of
+    the tile is element (p // cols) * ld_out + p % cols of `out` (default: contiguous)"""
+    cols = n_px if cols is None else cols
+    ld_out = cols if ld_out is None else ld_out
+    check(lib().ltmi_logsum_frames(
+        int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), int(n_frames), int(n_px),
+        int(ld_tile), ctypes.c_void_p(out_ptr), int(cols), int(ld_out), ctypes.c_void_p(workspace_ptr),
+        _stream_ptr(stream)), 'ltmi_logsum_frames')
 
 
 def sum_sig(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, out_dtype,

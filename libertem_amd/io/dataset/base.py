@@ -245,7 +245,8 @@ class Negotiator:
             io_max_size = itemsize * prod(approx_partition_shape)
         depth = max(self._get_min_depth(udf, approx_partition_shape) for udf in udfs)
         methods = [udf.get_method() for udf in udfs]
-        if any(m in (UDFMethod.FRAME, UDFMethod.PARTITION) for m in methods):
+        if any(m in (UDFMethod.FRAME, UDFMethod.PARTITION) for m in methods) \
+                or any(getattr(udf, 'WHOLE_FRAME_TILES', False) for udf in udfs):
             base_shape = ds_sig_shape
         else:
             base_shape = tuple(dataset.get_base_shape(roi))[-len(ds_sig_shape):]

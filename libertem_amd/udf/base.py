@@ -573,6 +573,11 @@ class UDF(UDFBase):
     #: over the resident array) -- other UDFs are handed the gathered frames.
     ACCEPTS_ROW_VIEWS = False
 
+    #: True: `process_tile` is handed whole frames -- the negotiator takes the full signal shape as the
+    #: base shape, as it does for `process_frame` / `process_partition` UDFs.  A tileshape forced on the
+    #: dataset still wins; such UDFs check `meta.sig_sliced_tiles` themselves.
+    WHOLE_FRAME_TILES = False
+
     def __init__(self, **kwargs):
         super().__init__()
         self._kwargs = kwargs
