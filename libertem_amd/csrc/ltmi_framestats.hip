@@ -19,7 +19,7 @@
 //                 last chunk, folds it into the float32 buffer.  No atomics: bitwise repeatable.
 // The compute dtype is np.result_type(float32, stored dtype): float for <= 16-bit integers and float32,
 // double for 32-bit integers and float64.
-#include "ltmi_common.h"
+#include "ltmi_tiles.h"
 
 namespace ltmi {
 namespace {
@@ -159,8 +159,7 @@ k_frame_min(const T *__restrict__ tile, int64_t ld, int64_t n_px,
             typename Compute<T>::type *__restrict__ mins) {
     typedef typename Compute<T>::type CT;
     constexpr int VEC = 16 / sizeof(T);
-    typedef T vec_a __attribute__((ext_vector_type(VEC)));
-    typedef vec_a vec_t __attribute__((aligned(sizeof(T))));
+    typedef tile_vec_t<T, VEC> vec_t;
     const T *fr = tile + (int64_t)blockIdx.x * ld;
     CT m = __builtin_inf();
     const int64_t n_vec = n_px / VEC;
@@ -201,8 +200,7 @@ __global__ void __launch_bounds__(FS_BLOCK)
 k_logsum_slab(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_px, int64_t per,
               const typename Compute<T>::type *__restrict__ mins, double *__restrict__ ws) {
     typedef typename Compute<T>::type CT;
-    typedef T vec_a __attribute__((ext_vector_type(VEC)));
-    typedef vec_a vec_t __attribute__((aligned(sizeof(T))));
+    typedef tile_vec_t<T, VEC> vec_t;
     const int64_t p0 = ((int64_t)blockIdx.x * FS_BLOCK + threadIdx.x) * VEC;
     if (p0 >= n_px) return;
     const int64_t f0 = (int64_t)blockIdx.y * per;
@@ -319,37 +317,21 @@ extern "C" int ltmi_ring_moments(int device, const void *tile, int tile_dtype, i
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
     const int32_t *sp = (const int32_t *)spans;
-#define LTMI_RING(T, L) return run_ring<T, L>(tile, n_frames, width, ld_tile, sp, n_spans, n_ring, (float *)out, stream)
-    switch (tile_dtype) {
-        case LTMI_U8: LTMI_RING(uint8_t, 1);
-        case LTMI_I8: LTMI_RING(int8_t, 1);
-        case LTMI_U16: LTMI_RING(uint16_t, 1);
-        case LTMI_I16: LTMI_RING(int16_t, 1);
-        case LTMI_U32: LTMI_RING(uint32_t, 1);
-        case LTMI_I32: LTMI_RING(int32_t, 1);
-        case LTMI_F32: LTMI_RING(float, 1);
-        case LTMI_F64: LTMI_RING(double, 1);
-        case LTMI_C64: LTMI_RING(float, 2);
-        case LTMI_C128: LTMI_RING(double, 2);
-    }
-#undef LTMI_RING
-    LTMI_FAIL(LTMI_E_DTYPE, "ltmi_ring_moments: unsupported tile dtype %s", dtype_name(tile_dtype));
+    constexpr unsigned TILES = DT_INT8_32 | DT_FLOAT | DT_CPLX;
+    if (!dtype_in(tile_dtype, TILES))
+        LTMI_FAIL(LTMI_E_DTYPE, "ltmi_ring_moments: unsupported tile dtype %s", dtype_name(tile_dtype));
+    return dispatch_tile<TILES>(tile_dtype, [&](auto part) {
+        return run_ring<LTMI_PART_T(part), LTMI_PART_L(part)>(tile, n_frames, width, ld_tile, sp, n_spans,
+                                                              n_ring, (float *)out, stream);
+    });
 }
 
-static int logsum_elem(int tile_dtype) {
-    switch (tile_dtype) {
-        case LTMI_U8: case LTMI_I8: return 1;
-        case LTMI_U16: case LTMI_I16: return 2;
-        case LTMI_U32: case LTMI_I32: case LTMI_F32: return 4;
-        case LTMI_F64: return 8;
-    }
-    return 0;
-}
+// the frames logsum takes: no complex ones (the reference cannot cast their terms to float32 either)
+constexpr unsigned LOGSUM_TILES = DT_INT8_32 | DT_FLOAT;
 
 extern "C" int64_t ltmi_logsum_workspace(int64_t n_frames, int64_t n_px, int tile_dtype) {
-    const int elem = logsum_elem(tile_dtype);
-    if (n_frames <= 0 || n_px <= 0 || elem == 0) return 0;
-    return logsum_ws_bytes(logsum_plan(n_frames, n_px, elem), n_px);
+    if (n_frames <= 0 || n_px <= 0 || !dtype_in(tile_dtype, LOGSUM_TILES)) return 0;
+    return logsum_ws_bytes(logsum_plan(n_frames, n_px, dtype_size(tile_dtype)), n_px);
 }
 
 extern "C" int ltmi_logsum_frames(int device, const void *tile, int tile_dtype, int64_t n_frames,
@@ -357,28 +339,16 @@ extern "C" int ltmi_logsum_frames(int device, const void *tile, int tile_dtype, 
                                   void *workspace, void *stream_) {
     if (n_frames < 0 || n_px < 0 || ld_tile < n_px)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_logsum_frames: bad shape");
-    if (n_px > 0 && (cols <= 0 || n_px % cols != 0 || ld_out < cols))
-        LTMI_FAIL(LTMI_E_SHAPE, "ltmi_logsum_frames: cols %lld / ld_out %lld do not fit %lld pixels",
-                  (long long)cols, (long long)ld_out, (long long)n_px);
-    if (logsum_elem(tile_dtype) == 0)
+    if (int rc = check_sig_slice("ltmi_logsum_frames", n_px, cols, ld_out)) return rc;
+    if (!dtype_in(tile_dtype, LOGSUM_TILES))
         LTMI_FAIL(LTMI_E_DTYPE, "ltmi_logsum_frames: unsupported tile dtype %s", dtype_name(tile_dtype));
     if (n_frames == 0 || n_px == 0) return LTMI_OK;
     if (!tile || !out || !workspace)
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_logsum_frames: null pointer");
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-    float *o = (float *)out;
-#define LTMI_LOGSUM(T) return run_logsum<T>(tile, n_frames, n_px, ld_tile, o, cols, ld_out, workspace, stream)
-    switch (tile_dtype) {
-        case LTMI_U8: LTMI_LOGSUM(uint8_t);
-        case LTMI_I8: LTMI_LOGSUM(int8_t);
-        case LTMI_U16: LTMI_LOGSUM(uint16_t);
-        case LTMI_I16: LTMI_LOGSUM(int16_t);
-        case LTMI_U32: LTMI_LOGSUM(uint32_t);
-        case LTMI_I32: LTMI_LOGSUM(int32_t);
-        case LTMI_F32: LTMI_LOGSUM(float);
-        case LTMI_F64: LTMI_LOGSUM(double);
-    }
-#undef LTMI_LOGSUM
-    LTMI_FAIL(LTMI_E_DTYPE, "ltmi_logsum_frames: unsupported tile dtype %s", dtype_name(tile_dtype));
+    return dispatch_tile<LOGSUM_TILES>(tile_dtype, [&](auto part) {
+        return run_logsum<LTMI_PART_T(part)>(tile, n_frames, n_px, ld_tile, (float *)out, cols, ld_out,
+                                             workspace, stream);
+    });
 }

@@ -15,7 +15,7 @@
 //                    pairwise update and folds the result into the running buffers:
 //                      varsum += varsum_b + n_b |delta| |delta'|,
 //                      delta = mean_b - mean_a, delta' = mean_b - mean_new.
-#include "ltmi_common.h"
+#include "ltmi_tiles.h"
 
 namespace ltmi {
 namespace {
@@ -23,17 +23,14 @@ namespace {
 constexpr int MOM_BLOCK = 256;
 
 // slabs: the frames of a tile in `fsplit` slabs of `per` frames (the last one may be shorter, none
-// is empty).  Independent of the tile dtype so that the workspace query and the launch agree.
+// is empty)
 struct Slabs {
     int fsplit;
     int64_t per;
 };
 
 Slabs moment_slabs(int64_t n_frames, int64_t n_px) {
-    const int64_t px_blocks = (n_px + 2047) / 2048;
-    int64_t want = (2048 + px_blocks - 1) / px_blocks;      // aim at >= 2048 workgroups
-    want = std::max<int64_t>(1, std::min<int64_t>(want, n_frames / 8));
-    want = std::min<int64_t>(want, 256);
+    const int64_t want = frames_split(n_frames, n_px);
     Slabs s;
     s.per = (n_frames + want - 1) / want;
     s.fsplit = (int)((n_frames + s.per - 1) / s.per);       // no empty slab
@@ -64,8 +61,7 @@ __global__ void __launch_bounds__(MOM_BLOCK)
 k_moments_slab(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_cols,
                int64_t per, double *__restrict__ ws) {
     static_assert(VEC % L == 0, "a thread owns whole pixels");
-    typedef T vec_a __attribute__((ext_vector_type(VEC)));
-    typedef vec_a vec_t __attribute__((aligned(sizeof(T))));   // rows at any element alignment
+    typedef tile_vec_t<T, VEC> vec_t;
     const int64_t c0 = ((int64_t)blockIdx.x * MOM_BLOCK + threadIdx.x) * VEC;
     if (c0 >= n_cols) return;
     const int64_t f0 = (int64_t)blockIdx.y * per;
@@ -237,7 +233,7 @@ using namespace ltmi;
 
 extern "C" int64_t ltmi_moments_workspace(int64_t n_frames, int64_t n_px, int tile_dtype) {
     if (n_frames <= 0 || n_px <= 0) return 0;
-    const int L = (tile_dtype == LTMI_C64 || tile_dtype == LTMI_C128) ? 2 : 1;
+    const int L = dtype_in(tile_dtype, DT_CPLX) ? 2 : 1;
     const Slabs sl = moment_slabs(n_frames, n_px);
     return (int64_t)sl.fsplit * (L + 1) * n_px * (int64_t)sizeof(double);
 }
@@ -248,14 +244,12 @@ extern "C" int ltmi_moments_frames(int device, const void *tile, int tile_dtype,
                                    int64_t ld_out, void *workspace, void *stream_) {
     if (n_frames < 0 || n_px < 0 || ld_tile < n_px || n_prev < 0)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_moments_frames: bad shape");
-    if (n_px > 0 && (cols <= 0 || n_px % cols != 0 || ld_out < cols))
-        LTMI_FAIL(LTMI_E_SHAPE, "ltmi_moments_frames: cols %lld / ld_out %lld do not fit %lld pixels",
-                  (long long)cols, (long long)ld_out, (long long)n_px);
+    if (int rc = check_sig_slice("ltmi_moments_frames", n_px, cols, ld_out)) return rc;
     if (n_frames == 0 || n_px == 0) return LTMI_OK;
     if (!tile || !sum || !varsum || !workspace)
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_moments_frames: null pointer");
-    const bool cplx_tile = tile_dtype == LTMI_C64 || tile_dtype == LTMI_C128;
-    const bool cplx_sum = sum_dtype == LTMI_C64 || sum_dtype == LTMI_C128;
+    const bool cplx_tile = dtype_in(tile_dtype, DT_CPLX);
+    const bool cplx_sum = dtype_in(sum_dtype, DT_CPLX);
     const bool sum_ok = sum_dtype == LTMI_F32 || sum_dtype == LTMI_F64 || cplx_sum;
     const bool var_ok = varsum_dtype == LTMI_F32 || varsum_dtype == LTMI_F64;
     if (!sum_ok || !var_ok || cplx_tile != cplx_sum)
@@ -263,21 +257,13 @@ extern "C" int ltmi_moments_frames(int device, const void *tile, int tile_dtype,
                   dtype_name(tile_dtype), dtype_name(sum_dtype), dtype_name(varsum_dtype));
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-#define LTMI_MOM(T, L)                                                                              \
-    return run_moments<T, L>(tile, n_frames, n_px, ld_tile, n_prev, sum, sum_dtype, varsum,          \
-                             varsum_dtype, cols, ld_out, workspace, stream)
-    switch (tile_dtype) {
-        case LTMI_U8: LTMI_MOM(uint8_t, 1);
-        case LTMI_I8: LTMI_MOM(int8_t, 1);
-        case LTMI_U16: LTMI_MOM(uint16_t, 1);
-        case LTMI_I16: LTMI_MOM(int16_t, 1);
-        case LTMI_U32: LTMI_MOM(uint32_t, 1);
-        case LTMI_I32: LTMI_MOM(int32_t, 1);
-        case LTMI_F32: LTMI_MOM(float, 1);
-        case LTMI_F64: LTMI_MOM(double, 1);
-        case LTMI_C64: LTMI_MOM(float, 2);
-        case LTMI_C128: LTMI_MOM(double, 2);
-    }
-#undef LTMI_MOM
-    LTMI_FAIL(LTMI_E_DTYPE, "ltmi_moments_frames: unsupported tile dtype %s", dtype_name(tile_dtype));
+    // 8- to 32-bit integers, floats and complex frames
+    constexpr unsigned TILES = DT_INT8_32 | DT_FLOAT | DT_CPLX;
+    if (!dtype_in(tile_dtype, TILES))
+        LTMI_FAIL(LTMI_E_DTYPE, "ltmi_moments_frames: unsupported tile dtype %s", dtype_name(tile_dtype));
+    return dispatch_tile<TILES>(tile_dtype, [&](auto part) {
+        return run_moments<LTMI_PART_T(part), LTMI_PART_L(part)>(
+            tile, n_frames, n_px, ld_tile, n_prev, sum, sum_dtype, varsum, varsum_dtype, cols, ld_out,
+            workspace, stream);
+    });
 }

@@ -6,7 +6,7 @@
 //
 // All three are pure HBM streams: 16-byte coalesced loads, conversion in registers,
 // wavefront (64-lane) shuffle reduction, no atomics (deterministic).
-#include "ltmi_common.h"
+#include "ltmi_tiles.h"
 
 namespace ltmi {
 
@@ -31,10 +31,7 @@ k_sum_sig(const T *__restrict__ tile, int64_t ld, int64_t n_px, A *__restrict__ 
     const T *row = tile + f * ld;
     A acc0 = 0, acc1 = 0;
     if (VEC > 1) {
-        // (element-aligned only: rows of odd length start at any element boundary; the target has
-        // unaligned access enabled, the load stays one global_load_dwordx4)
-        typedef T vec_a __attribute__((ext_vector_type(VEC)));
-        typedef vec_a vec_t __attribute__((aligned(sizeof(T))));
+        typedef tile_vec_t<T, VEC> vec_t;
         const int64_t nvec = n_px / VEC;
         const vec_t *vrow = (const vec_t *)row;
         int64_t i = threadIdx.x;
@@ -106,8 +103,7 @@ template <typename T, typename A, int VEC>
 __global__ void __launch_bounds__(256)
 k_sum_frames(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_px,
              A *__restrict__ dst, int64_t dst_stride_split, int fsplit, int accumulate_direct) {
-    typedef T vec_a __attribute__((ext_vector_type(VEC)));
-    typedef vec_a vec_t __attribute__((aligned(sizeof(T))));     // rows at any element alignment
+    typedef tile_vec_t<T, VEC> vec_t;
     const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VEC;
     if (p0 >= n_px) return;
     const int64_t per = (n_frames + fsplit - 1) / fsplit;
@@ -190,14 +186,6 @@ k_gather_rows(const V *__restrict__ src, int64_t ld_src_v, const int64_t *__rest
         d[i] = __builtin_nontemporal_load(s + i);
 }
 
-static int frames_split(int64_t n_frames, int64_t n_px) {
-    // independent of the tile dtype so that the workspace query and the launch always agree
-    const int64_t px_blocks = (n_px + 2047) / 2048;
-    int64_t want = (2048 + px_blocks - 1) / px_blocks;      // aim at >= 2048 workgroups
-    want = std::max<int64_t>(1, std::min<int64_t>(want, n_frames / 8));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(want, 256));
-}
-
 template <typename T> constexpr int vec_for() { return sizeof(T) >= 16 ? 1 : (int)(16 / sizeof(T)); }
 
 template <typename T, typename A>
@@ -241,29 +229,19 @@ static int run_sum_frames(const void *tile, int64_t n_frames, int64_t n_px, int6
     return LTMI_OK;
 }
 
-static int tile_vec(int dt) {
-    const int s = dtype_size(dt);
-    return s >= 16 ? 1 : 16 / s;
-}
-
 }  // namespace ltmi
 
 using namespace ltmi;
 
-#define LTMI_DISPATCH_TILE(FN, A, ...)                                                          \
-    switch (tile_dtype) {                                                                        \
-        case LTMI_BOOL:                                                                          \
-        case LTMI_U8: return FN<uint8_t, A>(__VA_ARGS__);                                       \
-        case LTMI_I8: return FN<int8_t, A>(__VA_ARGS__);                                        \
-        case LTMI_U16: return FN<uint16_t, A>(__VA_ARGS__);                                     \
-        case LTMI_I16: return FN<int16_t, A>(__VA_ARGS__);                                      \
-        case LTMI_U32: return FN<uint32_t, A>(__VA_ARGS__);                                     \
-        case LTMI_I32: return FN<int32_t, A>(__VA_ARGS__);                                      \
-        case LTMI_U64: return FN<uint64_t, A>(__VA_ARGS__);                                     \
-        case LTMI_I64: return FN<int64_t, A>(__VA_ARGS__);                                      \
-        case LTMI_F32: return FN<float, A>(__VA_ARGS__);                                        \
-        case LTMI_F64: return FN<double, A>(__VA_ARGS__);                                       \
-    }
+// real frames of every stored dtype (complex ones take routes of their own); RUN<T, A>(...) for the
+// tile's part type T and the accumulate type A, falling through for a dtype outside the set
+constexpr unsigned REAL_TILES = DT_BOOL | DT_INT8_32 | DT_INT64 | DT_FLOAT;
+constexpr unsigned INT_TILES = DT_BOOL | DT_INT8_32 | DT_INT64;
+#define LTMI_DISPATCH_TILE(SET, RUN, A, ...)                                                     \
+    if (dtype_in(tile_dtype, SET))                                                               \
+        return dispatch_tile<SET>(tile_dtype, [&](auto part) {                                   \
+            return RUN<LTMI_PART_T(part), A>(__VA_ARGS__);                                       \
+        });
 
 extern "C" int ltmi_sum_sig(int device, const void *tile, int tile_dtype, int64_t n_frames,
                             int64_t n_px, int64_t ld_tile, void *out, int out_dtype, int accumulate,
@@ -294,9 +272,9 @@ extern "C" int ltmi_sum_sig(int device, const void *tile, int tile_dtype, int64_
         return LTMI_OK;
     }
     if (out_dtype == LTMI_F32) {
-        LTMI_DISPATCH_TILE(run_sum_sig, float, tile, n_frames, n_px, ld_tile, out, accumulate, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_sig, float, tile, n_frames, n_px, ld_tile, out, accumulate, stream)
     } else if (out_dtype == LTMI_F64) {
-        LTMI_DISPATCH_TILE(run_sum_sig, double, tile, n_frames, n_px, ld_tile, out, accumulate, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_sig, double, tile, n_frames, n_px, ld_tile, out, accumulate, stream)
     }
     LTMI_FAIL(LTMI_E_DTYPE, "ltmi_sum_sig: unsupported dtypes tile=%s out=%s", dtype_name(tile_dtype),
               dtype_name(out_dtype));
@@ -309,8 +287,8 @@ extern "C" int ltmi_sum_sig(int device, const void *tile, int tile_dtype, int64_
 //   complex out, real tile    : real sums into a temporary, stored into the real parts
 //   integer out  : accumulate in int64 (exact), store truncated = NumPy's wrap-around in the narrower
 //                  type (udf/sum.py:38-48 with SumUDF(dtype=<integer>) on integer frames)
-static bool is_int_dtype(int dt) { return dt >= LTMI_BOOL && dt <= LTMI_I64; }
-static bool is_cplx_dtype(int dt) { return dt == LTMI_C64 || dt == LTMI_C128; }
+static bool is_int_dtype(int dt) { return dtype_in(dt, INT_TILES); }
+static bool is_cplx_dtype(int dt) { return dtype_in(dt, DT_CPLX); }
 
 static int64_t split_bytes(int64_t n_frames, int64_t n_cols, int acc_size) {
     const int fsplit = frames_split(n_frames, n_cols);
@@ -367,7 +345,6 @@ extern "C" int ltmi_sum_frames(int device, const void *tile, int tile_dtype, int
     if (!tile || !out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_sum_frames: null pointer");
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-    (void)tile_vec;
     if (is_cplx_dtype(tile_dtype)) {
         // complex frames are 2 * n_px real columns (udf/sum.py:38-40: the result keeps the complex dtype)
         const int rt = tile_dtype == LTMI_C64 ? LTMI_F32 : LTMI_F64;
@@ -384,25 +361,15 @@ extern "C" int ltmi_sum_frames(int device, const void *tile, int tile_dtype, int
                   dtype_name(tile_dtype), dtype_name(out_dtype));
     }
     if (out_dtype == LTMI_F32) {
-        LTMI_DISPATCH_TILE(run_sum_frames, float, tile, n_frames, n_px, ld_tile, out, accumulate, workspace, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_frames, float, tile, n_frames, n_px, ld_tile, out, accumulate, workspace, stream)
     } else if (out_dtype == LTMI_F64) {
-        LTMI_DISPATCH_TILE(run_sum_frames, double, tile, n_frames, n_px, ld_tile, out, accumulate, workspace, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_frames, double, tile, n_frames, n_px, ld_tile, out, accumulate, workspace, stream)
     } else if (out_dtype == LTMI_C64) {
-        LTMI_DISPATCH_TILE(run_sum_frames_cast, float, tile, n_frames, n_px, ld_tile, out, LTMI_F32, 2, accumulate, workspace, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_frames_cast, float, tile, n_frames, n_px, ld_tile, out, LTMI_F32, 2, accumulate, workspace, stream)
     } else if (out_dtype == LTMI_C128) {
-        LTMI_DISPATCH_TILE(run_sum_frames_cast, double, tile, n_frames, n_px, ld_tile, out, LTMI_F64, 2, accumulate, workspace, stream)
-    } else if (is_int_dtype(out_dtype) && out_dtype != LTMI_BOOL && is_int_dtype(tile_dtype)) {
-        switch (tile_dtype) {
-            case LTMI_BOOL:
-            case LTMI_U8: return run_sum_frames_cast<uint8_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_I8: return run_sum_frames_cast<int8_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_U16: return run_sum_frames_cast<uint16_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_I16: return run_sum_frames_cast<int16_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_U32: return run_sum_frames_cast<uint32_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_I32: return run_sum_frames_cast<int32_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_U64: return run_sum_frames_cast<uint64_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-            case LTMI_I64: return run_sum_frames_cast<int64_t, int64_t>(tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream);
-        }
+        LTMI_DISPATCH_TILE(REAL_TILES, run_sum_frames_cast, double, tile, n_frames, n_px, ld_tile, out, LTMI_F64, 2, accumulate, workspace, stream)
+    } else if (is_int_dtype(out_dtype) && out_dtype != LTMI_BOOL) {
+        LTMI_DISPATCH_TILE(INT_TILES, run_sum_frames_cast, int64_t, tile, n_frames, n_px, ld_tile, out, out_dtype, 1, accumulate, workspace, stream)
     }
     LTMI_FAIL(LTMI_E_DTYPE, "ltmi_sum_frames: unsupported dtypes tile=%s out=%s",
               dtype_name(tile_dtype), dtype_name(out_dtype));
@@ -511,9 +478,9 @@ extern "C" int ltmi_correct(int device, const void *tile, int tile_dtype, int64_
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
     if (out_dtype == LTMI_F32) {
-        LTMI_DISPATCH_TILE(run_correct, float, tile, n_frames, n_px, ld_tile, dark, gain, out, ld_out, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_correct, float, tile, n_frames, n_px, ld_tile, dark, gain, out, ld_out, stream)
     } else if (out_dtype == LTMI_F64) {
-        LTMI_DISPATCH_TILE(run_correct, double, tile, n_frames, n_px, ld_tile, dark, gain, out, ld_out, stream)
+        LTMI_DISPATCH_TILE(REAL_TILES, run_correct, double, tile, n_frames, n_px, ld_tile, dark, gain, out, ld_out, stream)
     }
     LTMI_FAIL(LTMI_E_DTYPE, "ltmi_correct: unsupported dtypes tile=%s out=%s", dtype_name(tile_dtype),
               dtype_name(out_dtype));
@@ -692,25 +659,17 @@ extern "C" int ltmi_add2d(int device, void *dest, int64_t ld_dest, const void *s
     if (rows * cols > ((int64_t)1 << 39)) LTMI_FAIL(LTMI_E_SHAPE, "ltmi_add2d: too many elements");
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-    switch (dtype) {                    // integers wrap around like NumPy's `+=`
-        case LTMI_BOOL: case LTMI_U8: case LTMI_I8:
-            launch_add2d<uint8_t>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_U16: case LTMI_I16:
-            launch_add2d<uint16_t>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_U32: case LTMI_I32:
-            launch_add2d<uint32_t>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_U64: case LTMI_I64:
-            launch_add2d<uint64_t>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_F32:
-            launch_add2d<float>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_F64:
-            launch_add2d<double>(dest, ld_dest, src, ld_src, rows, cols, negate, stream); break;
-        case LTMI_C64:                  // complex = pairs of reals
-            launch_add2d<float>(dest, 2 * ld_dest, src, 2 * ld_src, rows, 2 * cols, negate, stream);
-            break;
-        case LTMI_C128:
-            launch_add2d<double>(dest, 2 * ld_dest, src, 2 * ld_src, rows, 2 * cols, negate, stream);
-            break;
+    const int parts = is_cplx_dtype(dtype) ? 2 : 1;        // complex = pairs of reals
+    const int64_t ld_d = parts * ld_dest, ld_s = parts * ld_src, n_cols = parts * cols;
+    if (dtype == LTMI_F32 || dtype == LTMI_C64)
+        launch_add2d<float>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream);
+    else if (dtype == LTMI_F64 || dtype == LTMI_C128)
+        launch_add2d<double>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream);
+    else switch (is_int_dtype(dtype) ? dtype_size(dtype) : 0) {     // integers wrap around like NumPy's `+=`
+        case 1: launch_add2d<uint8_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
+        case 2: launch_add2d<uint16_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
+        case 4: launch_add2d<uint32_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
+        case 8: launch_add2d<uint64_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
         default:
             LTMI_FAIL(LTMI_E_DTYPE, "ltmi_add2d: unsupported dtype %d", dtype);
     }

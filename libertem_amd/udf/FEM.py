@@ -7,14 +7,13 @@ pixels where the difference is 1), handed to the device as row spans (row, x0, x
 `ltmi_ring_moments` reduces each frame of a tile in one workgroup (float64 sums about the frame's first
 ring pixel); on a CPU executor NumPy computes `np.std(frame[mask == 1])` like the reference.
 """
-import warnings
-
 import numpy as np
 
-from libertem_amd.common.hiparray import HipArray
-from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.masks import _make_circular_mask
 from libertem_amd.udf.base import UDF
+from libertem_amd.udf.device import (
+    check_device_args, check_whole_frames, float_frames, quiet_floats, runs_on_hip,
+)
 
 
 def ring_mask(center, rad_in, rad_out, sig_shape):
@@ -33,16 +32,6 @@ def ring_spans(mask):
     rows, starts = np.nonzero(d == 1)
     _, ends = np.nonzero(d == -1)
     return np.stack([rows, starts, ends], axis=1).astype(np.int32).reshape((-1, 3))
-
-
-def _check_whole_frames(udf, name):
-    if getattr(udf.meta, 'sig_sliced_tiles', False):
-        ds_shape = tuple(udf.meta.dataset_shape)
-        ts = udf.meta.tiling_scheme
-        shape = tuple(ts.shape) if ts is not None else None
-        raise ValueError(
-            f"{name} needs whole frames, but the dataset forces tileshape {shape} that cuts the frames of "
-            f"shape {ds_shape[-len(tuple(udf.meta.dataset_shape.sig)):]}")
 
 
 class FEMUDF(UDF):
@@ -82,15 +71,13 @@ class FEMUDF(UDF):
         return {'intensity': self.buffer(kind='nav', dtype='float32', where='device')}
 
     def get_task_data(self):
-        _check_whole_frames(self, 'FEMUDF')
+        check_whole_frames(self)
         sig = tuple(self.meta.dataset_shape.sig)
         if len(sig) != 2:
             raise ValueError(f"FEMUDF needs 2D frames, not {sig}")
         mask = ring_mask(self.params.center, self.params.rad_in, self.params.rad_out, sig)
-        if self.meta.array_backend == self.BACKEND_NUMPY:
+        if not runs_on_hip(self):
             return {'mask': mask, 'flat': np.flatnonzero(mask.reshape(-1)), 'spans': None}
-        if self.meta.array_backend != self.BACKEND_HIP:
-            raise HipRequiredError("FEMUDF needs BACKEND_HIP (an MI355X worker) or BACKEND_NUMPY (a CPU executor)")
         spans = ring_spans(mask)
         return {'mask': mask, 'flat': None, 'spans': spans, 'n_ring': int(np.count_nonzero(mask)),
                 'device_spans': {}}
@@ -106,20 +93,15 @@ class FEMUDF(UDF):
 
     def _process_tile_numpy(self, tile):
         # np.std(frame[mask == 1]) per frame (udf/FEM.py:65-66), in the reference's float frame dtype
-        tile = np.asarray(tile)
-        dtype = np.result_type(np.float32, tile.dtype)
-        if tile.dtype != dtype:
-            tile = tile.astype(dtype)
+        tile = float_frames(tile)
         vals = tile.reshape((tile.shape[0], -1))[:, self.task_data.flat]
-        with warnings.catch_warnings(), np.errstate(all='ignore'):
-            warnings.simplefilter('ignore', RuntimeWarning)
+        with quiet_floats():
             self.results.intensity[:] = np.std(vals, axis=1)
 
     def _process_tile_hip(self, tile):
         from libertem_amd import hip
         out = self.results.intensity
-        if not isinstance(tile, HipArray) or not isinstance(out, HipArray):
-            raise HipRequiredError("FEMUDF.process_tile expects device tiles and buffers")
+        check_device_args(self, tile, out)
         td = self.task_data
         spans = td.device_spans.get(tile.device)
         if spans is None:

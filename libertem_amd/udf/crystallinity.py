@@ -9,10 +9,10 @@ ONE batched hipFFT plus two small kernels (`ltmi_crystallinity`, csrc/ltmi_fft.h
 """
 import numpy as np
 
-from libertem_amd.common.hiparray import HipArray
 from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.masks import _make_circular_mask
 from libertem_amd.udf.base import UDF, UDFMethod
+from libertem_amd.udf.device import check_device_args
 
 #: workspace budget of one plan (f32 frames + complex64 half spectra), bytes: created only when a route needs it
 #: (hipFFT, corrected frames, the column workspace of 512 / 1024-pixel frames) -- frames of 1024 x 1024 want ~250 per
@@ -130,8 +130,7 @@ class CrystallinityUDF(UDF):
 
     def process_tile(self, tile):
         out = self.results.intensity
-        if not isinstance(tile, HipArray) or not isinstance(out, HipArray):
-            raise HipRequiredError("CrystallinityUDF.process_tile expects device tiles and buffers")
+        check_device_args(self, tile, out)
         td = self.task_data
         if tuple(tile.shape[1:]) != tuple(td.sig):
             raise ValueError(

@@ -7,16 +7,13 @@ integer pixels are converted first, so they never wrap.  On the device `ltmi_log
 of whole frames into the float32 buffer (per-frame min, then float64 sums of the terms per slab of
 frames, merged in a fixed order); on a CPU executor NumPy does the same sums.
 """
-import warnings
-
 import numpy as np
 
-from libertem_amd.common.math import prod
 from libertem_amd.common.buffers import HipSigView
-from libertem_amd.common.hiparray import HipArray
-from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.udf.base import UDF
-from libertem_amd.udf.FEM import _check_whole_frames
+from libertem_amd.udf.device import (
+    SigSlice, Workspace, check_device_args, check_whole_frames, float_frames, quiet_floats, runs_on_hip,
+)
 
 
 class LogsumUDF(UDF):
@@ -53,13 +50,11 @@ class LogsumUDF(UDF):
         if dt.kind == 'c':
             # the reference cannot cast the complex terms into its float32 buffer (udf/logsum.py:56-59)
             raise TypeError(f"LogsumUDF: complex input ({dt}) cannot be log-summed into a float32 buffer")
-        _check_whole_frames(self, 'LogsumUDF')
-        if self.meta.array_backend == self.BACKEND_HIP:
+        check_whole_frames(self)
+        if runs_on_hip(self):
             if dt.kind not in 'fiu' or (dt.kind in 'iu' and dt.itemsize > 4):
                 raise NotImplementedError(f"LogsumUDF on MI355X: input dtype {dt} is not supported")
-        elif self.meta.array_backend != self.BACKEND_NUMPY:
-            raise HipRequiredError("LogsumUDF needs BACKEND_HIP (an MI355X worker) or BACKEND_NUMPY (a CPU executor)")
-        return {'workspace': {}}
+        return {'workspace': Workspace()}
 
     def process_tile(self, tile):
         if tile.shape[0] == 0:
@@ -72,45 +67,28 @@ class LogsumUDF(UDF):
     def _process_tile_numpy(self, tile):
         # np.log(frame - np.min(frame) + 1) per frame (udf/logsum.py:54-59), in the float frame dtype,
         # summed in float64 and added to the float32 buffer
-        tile = np.asarray(tile)
+        tile = float_frames(tile)
         if tile.dtype.kind == 'c':
             raise TypeError(f"LogsumUDF: complex input ({tile.dtype}) cannot be log-summed into a float32 buffer")
-        dtype = np.result_type(np.float32, tile.dtype)
-        if tile.dtype != dtype:
-            tile = tile.astype(dtype)
         n = tile.shape[0]
         flat = tile.reshape((n, -1))
-        with warnings.catch_warnings(), np.errstate(all='ignore'):
-            warnings.simplefilter('ignore', RuntimeWarning)
+        with quiet_floats():
             mins = np.min(flat, axis=1, keepdims=True)
-            terms = np.log(flat - mins + dtype.type(1))
+            terms = np.log(flat - mins + tile.dtype.type(1))
         total = terms.sum(axis=0, dtype=np.float64).reshape(self.results.logsum.shape)
         out = self.results.logsum
         out[:] = out + total
 
-    def _workspace(self, device, nbytes):
-        import torch
-        ws = self.task_data.workspace
-        if ws.get('bytes', -1) < nbytes:
-            ws['t'] = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=f'cuda:{device}')
-            ws['bytes'] = nbytes
-        return ws['t'].data_ptr()
-
     def _process_tile_hip(self, tile):
         from libertem_amd import hip
         lv = self.results.logsum
-        if not isinstance(tile, HipArray) or not isinstance(lv, HipSigView):
-            raise HipRequiredError("LogsumUDF.process_tile expects device tiles and buffers")
-        arr = lv.array
+        check_device_args(self, tile, lv, kind=HipSigView)
         n = tile.shape[0]
-        sig_full = tuple(self.meta.dataset_shape.sig)
-        origin = tuple(lv.tile_slice.origin[-len(sig_full):])
-        shape = tuple(lv.tile_slice.shape.sig)
-        if shape != sig_full or any(o != 0 for o in origin):
-            raise ValueError(f"LogsumUDF needs whole frames, got a tile of sig shape {shape} at {origin}")
-        n_px = prod(sig_full)
-        ws = self._workspace(tile.device, hip.logsum_workspace(n, n_px, tile.dtype))
-        hip.logsum_frames(tile.device, tile.data_ptr(), tile.dtype, n, n_px, tile.ld, arr.data_ptr(), ws,
+        sl = SigSlice(lv, self.meta.dataset_shape.sig)
+        if not sl.whole_frames:
+            raise ValueError(f"LogsumUDF needs whole frames, got a tile of sig shape {sl.shape} at {sl.origin}")
+        ws = self.task_data.workspace.ptr(tile.device, hip.logsum_workspace(n, sl.n_px, tile.dtype))
+        hip.logsum_frames(tile.device, tile.data_ptr(), tile.dtype, n, sl.n_px, tile.ld, lv.array.data_ptr(), ws,
                           stream=self.meta.stream_ptr)
 
     def merge(self, dest, src):

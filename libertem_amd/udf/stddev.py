@@ -17,11 +17,9 @@ from collections import defaultdict
 
 import numpy as np
 
-from libertem_amd.common.math import prod
 from libertem_amd.common.buffers import HipSigView
-from libertem_amd.common.hiparray import HipArray
-from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.udf.base import UDF
+from libertem_amd.udf.device import SigSlice, Workspace, check_device_args, runs_on_hip
 
 
 def _merge_moments(dest_n, dest_sum, dest_varsum, src_n, src_sum, src_varsum):
@@ -103,15 +101,13 @@ class StdDevUDF(UDF):
         }
 
     def get_task_data(self):
-        if self.meta.array_backend == self.BACKEND_HIP:
+        if runs_on_hip(self):
             base, idt = self._base_dtype(), np.dtype(self.meta.input_dtype)
             if base.kind != 'f' or idt.kind not in 'fciu' or (idt.kind in 'iu' and idt.itemsize > 4):
                 raise NotImplementedError(
                     f"StdDevUDF on MI355X: input dtype {idt} with base dtype {base} is not supported "
                     "(float32 / float64 base; 8- to 32-bit integer, float or complex frames)")
-        elif self.meta.array_backend != self.BACKEND_NUMPY:
-            raise HipRequiredError("StdDevUDF needs BACKEND_HIP (an MI355X worker) or BACKEND_NUMPY (a CPU executor)")
-        return {'num_frames': defaultdict(int), 'workspace': {}}
+        return {'num_frames': defaultdict(int), 'workspace': Workspace()}
 
     def preprocess(self):
         # kept task instances run again: the frame counters belong to one run (the instance on
@@ -153,50 +149,22 @@ class StdDevUDF(UDF):
         else:
             _merge_moments(n_0, out_sum, out_var, n_1, tsum, tvar)
 
-    def _workspace(self, device, nbytes):
-        import torch
-        ws = self.task_data.workspace
-        if ws.get('bytes', -1) < nbytes:
-            ws['t'] = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=f'cuda:{device}')
-            ws['bytes'] = nbytes
-        return ws['t'].data_ptr()
-
     def _process_tile_hip(self, tile, n_0):
         from libertem_amd import hip
         sv, vv = self.results.sum, self.results.varsum
-        if not isinstance(tile, HipArray) or not isinstance(sv, HipSigView) \
-                or not isinstance(vv, HipSigView):
-            raise HipRequiredError("StdDevUDF.process_tile expects device tiles and buffers")
+        check_device_args(self, tile, sv, vv, kind=HipSigView)
         s_arr, v_arr = sv.array, vv.array
         n = tile.shape[0]
-        sig_full = tuple(self.meta.dataset_shape.sig)
-        s_origin = tuple(sv.tile_slice.origin[-len(sig_full):])
-        s_shape = tuple(sv.tile_slice.shape.sig)
         device = tile.device
         sz, vz, tz = s_arr.dtype.itemsize, v_arr.dtype.itemsize, np.dtype(tile.dtype).itemsize
-        strides = [prod(sig_full[k + 1:]) for k in range(len(sig_full))]
-
-        def launch(tile_off, n_px, out_off, cols, ld_out):
-            ws = self._workspace(device, hip.moments_workspace(n, n_px, tile.dtype))
+        # a partial-width sig slice: the kernel writes the strided sub-rectangle of the buffers
+        # directly (rows of `cols` pixels at stride ld_out), one launch per block
+        for tile_off, n_px, out_off, cols, ld_out in SigSlice(sv, self.meta.dataset_shape.sig).blocks():
+            ws = self.task_data.workspace.ptr(device, hip.moments_workspace(n, n_px, tile.dtype))
             hip.moments_frames(device, tile.data_ptr() + tile_off * tz, tile.dtype, n, n_px, tile.ld, n_0,
                                s_arr.data_ptr() + out_off * sz, s_arr.dtype,
                                v_arr.data_ptr() + out_off * vz, v_arr.dtype, ws,
                                cols=cols, ld_out=ld_out)
-
-        whole_rows = s_shape[1:] == sig_full[1:] and all(o == 0 for o in s_origin[1:])
-        if whole_rows:
-            n_px = prod(s_shape)
-            launch(0, n_px, s_origin[0] * strides[0], n_px, n_px)
-        else:
-            # partial-width sig slice: the kernel writes the strided sub-rectangle of the buffers
-            # directly (rows of `cols` pixels at stride ld_out); one launch per block of the outer
-            # sig axes (2D detectors: ONE launch)
-            rows, cols = s_shape[-2], s_shape[-1]
-            for outer in np.ndindex(*s_shape[:-2]):
-                off = sum((o + i) * st for o, i, st in zip(s_origin[:-2], outer, strides[:-2]))
-                off += s_origin[-2] * strides[-2] + s_origin[-1]
-                toff = sum(i * prod(s_shape[k + 1:]) for k, i in enumerate(outer))
-                launch(toff, rows * cols, off, cols, sig_full[-1])
 
     # --- merge ---------------------------------------------------------------------------------------
     def merge(self, dest, src):

@@ -4,11 +4,10 @@ Drop-in for the reference's libertem.udf.sum.SumUDF (udf/sum.py:6-58).
 """
 import numpy as np
 
-from libertem_amd.common.math import prod
 from libertem_amd.common.buffers import HipSigView
 from libertem_amd.common.hiparray import HipArray
-from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.udf.base import UDF
+from libertem_amd.udf.device import SigSlice, Workspace, check_device_args, runs_on_hip
 
 
 class SumUDF(UDF):
@@ -70,24 +69,14 @@ class SumUDF(UDF):
         return {'intensity': img}
 
     def get_task_data(self):
-        if self.meta.array_backend == self.BACKEND_NUMPY:
+        if not runs_on_hip(self):
             return {'workspace': None}
-        if self.meta.array_backend != self.BACKEND_HIP:
-            raise HipRequiredError("SumUDF needs BACKEND_HIP (an MI355X worker) or BACKEND_NUMPY (a CPU executor)")
         # result dtype = input dtype (udf/sum.py:38-40): float, complex, or -- SumUDF(dtype=<integer>)
         # on integer frames -- an integer with NumPy's wrap-around
         if np.dtype(self.meta.input_dtype).kind not in 'fciu':
             raise NotImplementedError(
                 f"SumUDF on MI355X: input dtype {self.meta.input_dtype} is not supported")
-        return {'workspace': {}}
-
-    def _workspace(self, device, nbytes):
-        import torch
-        ws = self.task_data.workspace
-        if ws.get('bytes', -1) < nbytes:
-            ws['t'] = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=f'cuda:{device}')
-            ws['bytes'] = nbytes
-        return ws['t'].data_ptr()
+        return {'workspace': Workspace()}
 
     def process_tile(self, tile):
         # results.intensity[sig slice] += tile.sum(axis=0)      (udf/sum.py:43-48)
@@ -96,45 +85,32 @@ class SumUDF(UDF):
             return
         from libertem_amd import hip
         view = self.results.intensity
-        if not isinstance(tile, HipArray) or not isinstance(view, HipSigView):
-            raise HipRequiredError("SumUDF.process_tile expects device tiles and buffers")
+        check_device_args(self, tile, view, kind=HipSigView)
         out = view.array
         odt = out.dtype
+        isz = odt.itemsize
         n = tile.shape[0]
-        sig_full = tuple(self.meta.dataset_shape.sig)
-        s_origin = tuple(view.tile_slice.origin[-len(sig_full):])
-        s_shape = tuple(view.tile_slice.shape.sig)
-        n_px = prod(s_shape)
+        sl = SigSlice(view, self.meta.dataset_shape.sig)
+        n_px = sl.n_px
         device = tile.device
         if getattr(self.meta, 'corrections_folded', False) and self.meta.tiling_scheme_idx == 0:
             self.results.n_raw[:] += n                  # once per group of frames (first sig slice)
-        ws = self._workspace(device, hip.sum_frames_workspace(n, n_px, odt))
-        whole_rows = s_shape[1:] == sig_full[1:] and all(o == 0 for o in s_origin[1:])
-        if whole_rows:
-            inner = prod(sig_full[1:])
-            out_ptr = out.data_ptr() + s_origin[0] * inner * odt.itemsize
-            hip.sum_frames(device, tile.data_ptr(), tile.dtype, n, n_px, tile.ld, out_ptr, odt,
-                           True, ws)
+        ws = self.task_data.workspace.ptr(device, hip.sum_frames_workspace(n, n_px, odt))
+        if sl.whole_rows:
+            out_off = next(sl.blocks())[2]
+            hip.sum_frames(device, tile.data_ptr(), tile.dtype, n, n_px, tile.ld,
+                           out.data_ptr() + out_off * isz, odt, True, ws)
         else:
             # partial-width sig slice: reduce into a temporary, add into the strided region
-            tmp = HipArray.zeros(s_shape, odt, device)
+            tmp = HipArray.zeros(sl.shape, odt, device)
             hip.sum_frames(device, tile.data_ptr(), tile.dtype, n, n_px, tile.ld, tmp.data_ptr(),
                            odt, False, ws)
             # out[sig slice] += tmp: rows of the innermost axis, one strided add per block of the
             # outer sig axes (2D detectors: ONE call)
-            isz = odt.itemsize
-            strides = [prod(sig_full[k + 1:]) for k in range(len(sig_full))]
-            if len(sig_full) == 1:
-                hip.add2d(device, out.data_ptr() + s_origin[0] * isz, sig_full[0], tmp.data_ptr(),
-                          s_shape[0], odt, 1, s_shape[0])
-            else:
-                rows, cols = s_shape[-2], s_shape[-1]
-                for outer in np.ndindex(*s_shape[:-2]):
-                    off = sum((o + i) * st for o, i, st in zip(s_origin[:-2], outer, strides[:-2]))
-                    off += s_origin[-2] * strides[-2] + s_origin[-1]
-                    toff = sum(i * prod(s_shape[k + 1:]) for k, i in enumerate(outer))
-                    hip.add2d(device, out.data_ptr() + off * isz, sig_full[-1],
-                              tmp.data_ptr() + toff * isz, cols, odt, rows, cols)
+            # (a 1D sig slice is always whole rows: it never comes here)
+            for tile_off, block_px, out_off, cols, ld_out in sl.blocks():
+                hip.add2d(device, out.data_ptr() + out_off * isz, ld_out,
+                          tmp.data_ptr() + tile_off * isz, cols, odt, block_px // cols, cols)
 
     def merge(self, dest, src):
         dest.intensity[:] += src.intensity                     # udf/sum.py:50-52

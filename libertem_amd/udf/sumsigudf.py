@@ -5,9 +5,8 @@ Drop-in for the reference's libertem.udf.sumsigudf.SumSigUDF (udf/sumsigudf.py:6
 import numpy as np
 
 from libertem_amd.common.math import prod
-from libertem_amd.common.hiparray import HipArray
-from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.udf.base import UDF
+from libertem_amd.udf.device import check_device_args, runs_on_hip
 
 
 class SumSigUDF(UDF):
@@ -29,11 +28,7 @@ class SumSigUDF(UDF):
             np.dtype(np.result_type(meta.input_dtype, np.float32)) == np.float32
 
     def get_task_data(self):
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            return {'engine': None}
-        if self.meta.array_backend != self.BACKEND_HIP:
-            raise HipRequiredError("SumSigUDF needs BACKEND_HIP (an MI355X worker) or BACKEND_NUMPY (a CPU executor)")
-        if getattr(self.meta, 'corrections_folded', False):
+        if runs_on_hip(self) and getattr(self.meta, 'corrections_folded', False):
             from libertem_amd.udf.masks import ApplyMasksEngine, _cached_container, _folded_plan
             sig = tuple(self.meta.dataset_shape.sig)
             ones = _ones_factory(sig)
@@ -52,8 +47,7 @@ class SumSigUDF(UDF):
             return
         from libertem_amd import hip
         out = self.results.intensity
-        if not isinstance(tile, HipArray) or not isinstance(out, HipArray):
-            raise HipRequiredError("SumSigUDF.process_tile expects device tiles and buffers")
+        check_device_args(self, tile, out)
         if out.dtype.kind not in 'fc':
             raise NotImplementedError(f"SumSigUDF: result dtype {out.dtype} not supported")
         n = tile.shape[0]
