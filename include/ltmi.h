@@ -275,7 +275,8 @@ int ltmi_logsum_frames(int device, const void *tile, int tile_dtype, int64_t n_f
                        void *stream);
 
 /* merge for sig-kind buffers: dest[i] += src[i]          (src/libertem/udf/sum.py:50-52);
- * every dtype of enum ltmi_dtype, integers wrap around like NumPy's `+=` */
+ * every dtype of enum ltmi_dtype but bool, integers wrap around like NumPy's `+=`.  LTMI_BOOL is
+ * LTMI_E_DTYPE, also for ltmi_add2d: NumPy's `+=` on bool is a logical or and its `-=` an error. */
 int ltmi_axpy(int device, void *dest, const void *src, int dtype, int64_t n, void *stream);
 /* dest[r, c] (+|-)= src[r, c] for r < rows, c < cols; leading dimensions in ELEMENTS; ld_src == 0
  * broadcasts one row.  Replaces the NumPy in-place arithmetic around the kernels:

@@ -665,13 +665,15 @@ extern "C" int ltmi_add2d(int device, void *dest, int64_t ld_dest, const void *s
         launch_add2d<float>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream);
     else if (dtype == LTMI_F64 || dtype == LTMI_C128)
         launch_add2d<double>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream);
-    else switch (is_int_dtype(dtype) ? dtype_size(dtype) : 0) {     // integers wrap around like NumPy's `+=`
+    // integers wrap around like NumPy's `+=`; bool is refused: NumPy's `+=` is a logical or there and its
+    // `-=` an error, which adding the bytes is not
+    else switch (is_int_dtype(dtype) && dtype != LTMI_BOOL ? dtype_size(dtype) : 0) {
         case 1: launch_add2d<uint8_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
         case 2: launch_add2d<uint16_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
         case 4: launch_add2d<uint32_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
         case 8: launch_add2d<uint64_t>(dest, ld_d, src, ld_s, rows, n_cols, negate, stream); break;
         default:
-            LTMI_FAIL(LTMI_E_DTYPE, "ltmi_add2d: unsupported dtype %d", dtype);
+            LTMI_FAIL(LTMI_E_DTYPE, "ltmi_add2d: unsupported dtype %s", dtype_name(dtype));
     }
     LTMI_HIP(hipGetLastError());
     return LTMI_OK;

@@ -610,9 +610,9 @@ def sum_sig(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, out_
         _stream_ptr(stream)), 'ltmi_sum_sig')
 
 
-#: dtypes ltmi_axpy / ltmi_add2d take (every dtype of the enum)
+#: dtypes ltmi_axpy / ltmi_add2d take (every dtype of the enum but bool, whose `+=` is a logical or)
 AXPY_DTYPES = frozenset(np.dtype(t) for t in (
-    'bool', 'u1', 'i1', 'u2', 'i2', 'u4', 'i4', 'u8', 'i8', 'f4', 'f8', 'c8', 'c16'))
+    'u1', 'i1', 'u2', 'i2', 'u4', 'i4', 'u8', 'i8', 'f4', 'f8', 'c8', 'c16'))
 
 
 def axpy(device, dest_ptr, src_ptr, dtype, n, stream=None):
