@@ -195,7 +195,10 @@ int ltmi_apply_masks_rows(ltmi_masks *m, const void *tile, int tile_dtype, const
  * Replaces ApplyMasksEngine.process_frame_shifted (src/libertem/udf/masks.py:85-124), one call per
  * tile instead of one per frame.  Dense handles only.  `shifts` is a DEVICE array of n_frames
  * (dy, dx) int32 pairs; frames are (sig_h, sig_w) row-major, sig_h * sig_w == the handle's n_px.
- * A positive dy moves the mask down relative to the frame; no overlap contributes 0.
+ * A positive dy moves the mask down relative to the frame; no overlap contributes 0.  Any int32 pair
+ * is a valid shift: |dy| >= sig_h or |dx| >= sig_w is "no overlap", however large.
+ * Only pixels inside the overlap are read: a NaN / Inf pixel that the shift cuts off does not exist
+ * for this product, one inside the overlap reaches every mask (0 * NaN = NaN), as in the reference.
  */
 int ltmi_apply_masks_shifted(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
                              int64_t ld_tile, int sig_h, int sig_w, const int32_t *shifts,
@@ -208,7 +211,15 @@ int ltmi_apply_masks_shifted(ltmi_masks *m, const void *tile, int tile_dtype, in
  * results: the f64 matrix-core kernel per group of frames with the same shift (one call for a tile
  * with a constant shift; up to 256 distinct shifts per tile, up to 4096 while a shift is shared by 8 frames on
  * average and the shifted images fit 4 GiB).  Falls back to the per-frame kernel
- * above (after uploading the shifts) for handles / tiles these paths do not take. */
+ * above (after uploading the shifts) for handles / tiles these paths do not take.
+ * Non-finite pixels: the matrix-core routes multiply the WHOLE frame with an image that is zero
+ * outside the overlap, which equals the product over the overlap for finite pixels only.  For
+ * float32 / float64 frames the frames with a non-finite result row are therefore listed on the
+ * device (no host synchronisation) and computed again by the per-frame kernel, so that the result
+ * is the one documented above on every route; with `accumulate` the product of such a tile is
+ * formed in a scratch buffer of the handle and added to `out` afterwards.  Integer frames run as
+ * they are.  LTMI_NONFINITE_GUARD=0 in the environment switches this off (timing ablation): a
+ * non-finite pixel anywhere in a frame then makes every result of that frame NaN on these routes. */
 int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
                                   int64_t ld_tile, int sig_h, int sig_w, const int32_t *shifts_host,
                                   void *out, int64_t ld_out, int accumulate, void *stream);

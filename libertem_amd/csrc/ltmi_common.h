@@ -40,6 +40,11 @@ static inline bool vector_loads_ok(const void *tile, int64_t ld_elems, size_t el
     return !aligned_only && ((uintptr_t)tile) % elem == 0;
 }
 
+// Shifted masks: a shift of sig or more in either direction leaves no overlap, whatever its size.  Kernels and image
+// builders clamp (dy, dx) to [-sig, sig] on entry, so that `sig + d`, `y1 - y0` and `y - d` stay inside int for every
+// int32 shift.
+__host__ __device__ static inline int clamp_shift(int d, int sig) { return d < -sig ? -sig : (d > sig ? sig : d); }
+
 // K split of the LDS-DMA kernels (one workgroup per CU at a time, 256 CUs): `wgs` workgroups at
 // ksplit = 1, each walking `n_slots` mask slots.  A split by ks makes ks x wgs workgroups of n_slots / ks
 // slots; the launch takes ceil(ks wgs / 256) rounds of (n_slots / ks + start-up) plus, for ks > 1, the
@@ -177,6 +182,14 @@ bool guard_wanted(const ltmi_masks *m, int tile_dtype);
 int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, void *out,
                 int64_t ld_out, int accumulate, hipStream_t stream);
 void guard_destroy(ltmi_masks *m);
+// the guard's pieces, for the shifted routes of ltmi_dense.hip: where the product goes, which result rows are
+// non-finite (lists on the device), the product to its place
+bool guard_wanted_shifted(const ltmi_masks *m, int tile_dtype);
+int guard_target(ltmi_masks *m, int64_t n_frames, void *out, int64_t ld_out, int accumulate, hipStream_t stream,
+                 void **target, int64_t *ld_target);
+int guard_list_rows(ltmi_masks *m, const void *target, int64_t ld_target, int64_t n_frames, hipStream_t stream,
+                    int **ctl, int32_t **list);
+int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, int accumulate, hipStream_t stream);
 // ltmi_apply_masks without the guard (ltmi_dense.hip)
 int apply_masks_unguarded(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
                           void *out, int64_t ld_out, int accumulate, hipStream_t stream);

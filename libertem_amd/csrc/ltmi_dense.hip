@@ -470,6 +470,8 @@ __global__ void k_build_image2(const float *__restrict__ src, float *__restrict_
 __global__ void k_build_image_shifted(const float *__restrict__ src, float *__restrict__ img,
                                       int64_t n_masks, int cpm, int sig_h, int sig_w, int dy, int dx,
                                       int n_chunks) {
+    dy = clamp_shift(dy, sig_h);
+    dx = clamp_shift(dx, sig_w);
     const int64_t n_px = (int64_t)sig_h * sig_w;
     const int64_t total = n_masks * cpm * n_px;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -493,6 +495,8 @@ __global__ void k_build_image_shifted(const float *__restrict__ src, float *__re
 __global__ void k_build_image_shifted_h16(const float *__restrict__ src, _Float16 *__restrict__ img,
                                           int64_t n_masks, int cpm, int sig_h, int sig_w, int dy, int dx,
                                           int n_chunks, const float *__restrict__ inv_scale) {
+    dy = clamp_shift(dy, sig_h);
+    dx = clamp_shift(dx, sig_w);
     const int64_t n_px = (int64_t)sig_h * sig_w;
     const int64_t total = n_masks * cpm * n_px;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -1315,47 +1319,54 @@ k_dense_generic(const TIn *__restrict__ tile, int64_t ld, int64_t n_frames, int6
         Store<S, A>::put(out + f * ld_out + k0 + threadIdx.x, red[threadIdx.x][0], accumulate != 0);
 }
 
-// shifted masks: block (256 threads) per (frame, group of 4 masks); threads walk the overlap region
+// shifted masks: block (256 threads) per (frame, group of 4 masks); threads walk the overlap region.
+// `sel` / `n_sel` (the non-finite guard's redo): a capped grid whose blocks stride over the frames sel[0 .. *n_sel).
 template <typename TIn, typename A, typename S>
 __global__ void __launch_bounds__(256)
 k_dense_shifted(const TIn *__restrict__ tile, int64_t ld, int sig_h, int sig_w,
                 const int32_t *__restrict__ shifts, const A *__restrict__ masks, int n_masks,
-                S *__restrict__ out, int64_t ld_out, int accumulate) {
+                S *__restrict__ out, int64_t ld_out, int accumulate, const int32_t *__restrict__ sel,
+                const int *__restrict__ n_sel) {
     __shared__ A red[GEN_MASKS][256];
-    const int64_t f = blockIdx.x;
     const int k0 = blockIdx.y * GEN_MASKS;
     const int nk = min(GEN_MASKS, n_masks - k0);
-    const int dy = shifts[2 * f], dx = shifts[2 * f + 1];
-    // frame rows [y0, y1) x cols [x0, x1) overlap the mask shifted by (dy, dx)
-    const int y0 = max(0, dy), y1 = min(sig_h, sig_h + dy);
-    const int x0 = max(0, dx), x1 = min(sig_w, sig_w + dx);
-    const int ow = max(0, x1 - x0), oh = max(0, y1 - y0);
-    const int64_t n_px = (int64_t)sig_h * sig_w;
-    A acc[GEN_MASKS];
+    // without a list: block x is frame x, once; with one: the blocks stride over the listed frames
+    const int64_t n_items = sel ? (int64_t)*n_sel : (int64_t)gridDim.x;
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int64_t f = sel ? (int64_t)sel[item] : item;
+        const int dy = clamp_shift(shifts[2 * f], sig_h), dx = clamp_shift(shifts[2 * f + 1], sig_w);
+        // frame rows [y0, y1) x cols [x0, x1) overlap the mask shifted by (dy, dx)
+        const int y0 = max(0, dy), y1 = sig_h + min(0, dy);
+        const int x0 = max(0, dx), x1 = sig_w + min(0, dx);
+        const int ow = max(0, x1 - x0), oh = max(0, y1 - y0);
+        const int64_t n_px = (int64_t)sig_h * sig_w;
+        A acc[GEN_MASKS];
 #pragma unroll
-    for (int k = 0; k < GEN_MASKS; ++k) acc[k] = AccOps<A>::zero();
-    const TIn *row = tile + f * ld;
-    for (int64_t i = threadIdx.x; i < (int64_t)ow * oh; i += 256) {
-        const int y = y0 + (int)(i / ow), x = x0 + (int)(i % ow);
-        const A v = Conv<A, TIn>::from(row[(int64_t)y * sig_w + x]);
-        const int64_t mp = (int64_t)(y - dy) * sig_w + (x - dx);
-#pragma unroll
-        for (int k = 0; k < GEN_MASKS; ++k)
-            if (k < nk) AccOps<A>::fma(acc[k], v, masks[(int64_t)(k0 + k) * n_px + mp]);
-    }
-#pragma unroll
-    for (int k = 0; k < GEN_MASKS; ++k) red[k][threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
+        for (int k = 0; k < GEN_MASKS; ++k) acc[k] = AccOps<A>::zero();
+        const TIn *row = tile + f * ld;
+        for (int64_t i = threadIdx.x; i < (int64_t)ow * oh; i += 256) {
+            const int y = y0 + (int)(i / ow), x = x0 + (int)(i % ow);
+            const A v = Conv<A, TIn>::from(row[(int64_t)y * sig_w + x]);
+            const int64_t mp = (int64_t)(y - dy) * sig_w + (x - dx);
 #pragma unroll
             for (int k = 0; k < GEN_MASKS; ++k)
-                red[k][threadIdx.x] = AccOps<A>::add(red[k][threadIdx.x], red[k][threadIdx.x + s]);
+                if (k < nk) AccOps<A>::fma(acc[k], v, masks[(int64_t)(k0 + k) * n_px + mp]);
         }
+#pragma unroll
+        for (int k = 0; k < GEN_MASKS; ++k) red[k][threadIdx.x] = acc[k];
         __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) {
+#pragma unroll
+                for (int k = 0; k < GEN_MASKS; ++k)
+                    red[k][threadIdx.x] = AccOps<A>::add(red[k][threadIdx.x], red[k][threadIdx.x + s]);
+            }
+            __syncthreads();
+        }
+        if ((int)threadIdx.x < nk)
+            Store<S, A>::put(out + f * ld_out + k0 + threadIdx.x, red[threadIdx.x][0], accumulate != 0);
+        __syncthreads();                           // (red is written again by the next listed frame)
     }
-    if ((int)threadIdx.x < nk)
-        Store<S, A>::put(out + f * ld_out + k0 + threadIdx.x, red[threadIdx.x][0], accumulate != 0);
 }
 
 }  // namespace ltmi
@@ -2111,8 +2122,18 @@ struct ShiftCache {
     int64_t *idx_dev = nullptr;
     size_t idx_cap = 0;
     std::vector<int64_t> idx_stage[STAGES];
+    // the shifts of the tile on the device: the per-frame kernel's, and the non-finite guard's redo
+    int32_t *shifts_dev = nullptr;
+    size_t shifts_cap = 0;
+    std::vector<int32_t> shifts_stage[STAGES];
+    int shifts_stage_at = 0;                            // (a ring of its own: a call may take a stage of each)
 };
 constexpr size_t SHIFT_CACHE_BYTES = (size_t)4 << 30;   // at most 4 GiB of shifted images per handle
+
+// (dy, dx) of frame f as the key of its image (as given: the builders clamp, the grouping of a tile stays what it was)
+static uint64_t shift_key(const int32_t *shifts_host, int64_t f) {
+    return ((uint64_t)(uint32_t)shifts_host[2 * f] << 32) | (uint32_t)shifts_host[2 * f + 1];
+}
 
 static void shift_cache_destroy(ltmi_masks *m) {
     ShiftCache *c = (ShiftCache *)m->shift_cache;
@@ -2123,6 +2144,7 @@ static void shift_cache_destroy(ltmi_masks *m) {
     if (c->res) (void)hipFree(c->res);
     if (c->idx_dev) (void)hipFree(c->idx_dev);
     if (c->rows_dev) (void)hipFree(c->rows_dev);
+    if (c->shifts_dev) (void)hipFree(c->shifts_dev);
     if (c->wg_img_dev) (void)hipFree((void *)c->wg_img_dev);
     delete c;
     m->shift_cache = nullptr;
@@ -2158,8 +2180,7 @@ static int launch_lds_shifted(ltmi_masks *m, const T *tile, int64_t n_frames, in
     std::vector<uint64_t> keys;
     std::vector<std::vector<int32_t>> members;
     for (int64_t f = 0; f < n_frames; ++f) {
-        const uint64_t key = ((uint64_t)(uint32_t)shifts_host[2 * f] << 32) |
-                             (uint32_t)shifts_host[2 * f + 1];
+        const uint64_t key = shift_key(shifts_host, f);
         auto it = group_of.find(key);
         int g;
         if (it == group_of.end()) {
@@ -2366,7 +2387,12 @@ static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t l
 
 // ---- generic launch ------------------------------------------------------------------------------
 // set by ltmi_apply_masks_shifted around the generic dispatch (per thread)
-struct ShiftCtx { const int32_t *shifts = nullptr; int sig_h = 0, sig_w = 0; };
+struct ShiftCtx {
+    const int32_t *shifts = nullptr;
+    int sig_h = 0, sig_w = 0;
+    const int32_t *sel = nullptr;       // the guard's redo: the listed frames only (k_dense_shifted)
+    const int *n_sel = nullptr;
+};
 static thread_local ShiftCtx g_shift;
 
 template <typename TIn, typename A, typename S>
@@ -2374,10 +2400,13 @@ static int launch_generic(ltmi_masks *m, const void *tile, int64_t n_frames, int
                           int64_t ld_out, int accumulate, hipStream_t stream) {
     dim3 grid((unsigned)n_frames, (unsigned)((m->n_masks + GEN_MASKS - 1) / GEN_MASKS));
     if (g_shift.shifts) {
+        if (g_shift.sel) grid.x = (unsigned)std::min<int64_t>(n_frames, 1024);   // (the list is short or empty)
         hipLaunchKernelGGL((k_dense_shifted<TIn, A, S>), grid, dim3(256), 0, stream,
                            (const TIn *)tile, ld, g_shift.sig_h, g_shift.sig_w, g_shift.shifts,
-                           (const A *)m->gmasks, (int)m->n_masks, (S *)out, ld_out, accumulate);
+                           (const A *)m->gmasks, (int)m->n_masks, (S *)out, ld_out, accumulate, g_shift.sel,
+                           g_shift.n_sel);
         LTMI_HIP(hipGetLastError());
+        if (g_shift.sel) return LTMI_OK;                  // (the route's name stays that of the product)
         snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_shifted<%s,%s> grid=(%u,%u)",
                  typeid(TIn).name(), typeid(A).name(), grid.x, grid.y);
         return LTMI_OK;
@@ -2636,8 +2665,7 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
     std::vector<uint64_t> keys;
     std::vector<std::vector<int64_t>> members;
     for (int64_t f = 0; f < n_frames; ++f) {
-        const uint64_t key = ((uint64_t)(uint32_t)shifts_host[2 * f] << 32) |
-                             (uint32_t)shifts_host[2 * f + 1];
+        const uint64_t key = shift_key(shifts_host, f);
         auto it = group_of.find(key);
         int g;
         if (it == group_of.end()) {
@@ -2764,6 +2792,32 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
     return LTMI_OK;
 }
 
+// the (dy, dx) of a tile to the handle's device list (a ring of host copies: an asynchronous copy of an earlier call
+// may still be reading its own)
+static int upload_shifts(ltmi_masks *m, const int32_t *shifts_host, int64_t n_frames, hipStream_t stream,
+                         const int32_t **shifts_dev) {
+    ShiftCache *c = (ShiftCache *)m->shift_cache;
+    if (!c) {
+        c = new (std::nothrow) ShiftCache();
+        if (!c) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
+        m->shift_cache = c;
+    }
+    const size_t need = (size_t)n_frames * 2;
+    if (c->shifts_cap < need) {
+        if (c->shifts_dev) LTMI_HIP(hipFree(c->shifts_dev));
+        c->shifts_dev = nullptr;
+        c->shifts_cap = need * 2;
+        LTMI_HIP(hipMalloc((void **)&c->shifts_dev, c->shifts_cap * sizeof(int32_t)));
+    }
+    c->shifts_stage_at = (c->shifts_stage_at + 1) % ShiftCache::STAGES;
+    std::vector<int32_t> &stage = c->shifts_stage[c->shifts_stage_at];
+    stage.assign(shifts_host, shifts_host + need);
+    LTMI_HIP(hipMemcpyAsync(c->shifts_dev, stage.data(), need * sizeof(int32_t),
+                            hipMemcpyHostToDevice, stream));
+    *shifts_dev = c->shifts_dev;
+    return LTMI_OK;
+}
+
 extern "C" int ltmi_apply_masks_shifted(ltmi_masks *m, const void *tile, int tile_dtype,
                                         int64_t n_frames, int64_t ld_tile, int sig_h, int sig_w,
                                         const int32_t *shifts, void *out, int64_t ld_out,
@@ -2782,12 +2836,13 @@ extern "C" int ltmi_apply_masks_shifted(ltmi_masks *m, const void *tile, int til
     if (!tile || !out || !shifts)
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_apply_masks_shifted: null pointer");
     LTMI_HIP(hipSetDevice(m->device));
+    if (m->guard) ltmi::guard_note_unchecked(m);
     g_shift.shifts = shifts;
     g_shift.sig_h = sig_h;
     g_shift.sig_w = sig_w;
     const int rc = apply_generic(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate,
                                  (hipStream_t)stream_);
-    g_shift.shifts = nullptr;
+    g_shift = ShiftCtx();
     return rc;
 }
 
@@ -2812,47 +2867,73 @@ extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, in
     hipStream_t stream = (hipStream_t)stream_;
     const size_t esz = (size_t)dtype_size(tile_dtype);
     const bool aligned = vector_loads_ok(tile, ld_tile, esz);
-    if (m->kind == 0 && aligned && m->n_px >= KC && n_frames < (1ll << 31)) {
+    if (m->guard) ltmi::guard_note_unchecked(m);
+    // Float frames on the routes that multiply WHOLE frames with the zero-filled image of the shifted stack: a
+    // non-finite pixel outside the overlap would reach every mask of its frame (0 * NaN), where the reference never
+    // reads it.  As in ltmi_guard.hip: the product (into the guard's scratch under `accumulate`, the old rows are
+    // not the product's), the frames with a non-finite result row listed on the device, those frames again by the
+    // overlap walk of k_dense_shifted, the scratch added to `out`.  Integer frames: the routes as they are.
+    const bool guarded = ltmi::guard_wanted_shifted(m, tile_dtype) && n_frames < (1ll << 31);
+    const bool lds_route = m->kind == 0 && aligned && m->n_px >= KC && n_frames < (1ll << 31);
+    const bool f64_route = m->img64 && tile_dtype != LTMI_C64 && tile_dtype != LTMI_C128 && n_frames < (1ll << 31);
+    void *target = out;
+    int64_t ld_t = ld_out;
+    int acc_t = accumulate;
+    const bool check = guarded && ((lds_route && tile_dtype == LTMI_F32) || f64_route);
+    if (check) {
+        const int rc = ltmi::guard_target(m, n_frames, out, ld_out, accumulate, stream, &target, &ld_t);
+        if (rc != LTMI_OK) return rc;
+        if (target != out) acc_t = 0;
+    }
+    auto redo_and_deliver = [&]() -> int {
+        if (!check) return LTMI_OK;
+        const int32_t *shifts_dev = nullptr;
+        int rc = upload_shifts(m, shifts_host, n_frames, stream, &shifts_dev);
+        if (rc != LTMI_OK) return rc;
+        int *n_listed = nullptr;
+        int32_t *listed = nullptr;
+        rc = ltmi::guard_list_rows(m, target, ld_t, n_frames, stream, &n_listed, &listed);
+        if (rc != LTMI_OK) return rc;
+        g_shift.shifts = shifts_dev;
+        g_shift.sig_h = sig_h;
+        g_shift.sig_w = sig_w;
+        g_shift.sel = listed;
+        g_shift.n_sel = n_listed;
+        rc = apply_generic(m, tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream);
+        g_shift = ShiftCtx();
+        if (rc != LTMI_OK) return rc;
+        const size_t len = strlen(m->last_kernel);
+        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
+        return ltmi::guard_deliver(m, out, ld_out, n_frames, accumulate, stream);
+    };
+    if (lds_route) {
         bool handled = false;
         int rc = LTMI_OK;
-        const int64_t ldo = (m->result_dtype == LTMI_C64) ? 2 * ld_out : ld_out;
+        const int cw = (m->result_dtype == LTMI_C64) ? 2 : 1;
+        const int64_t ldo = cw * ld_out;
         switch (tile_dtype) {
             case LTMI_U8: rc = launch_lds_shifted<uint8_t>(m, (const uint8_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
             case LTMI_I8: rc = launch_lds_shifted<int8_t>(m, (const int8_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
             case LTMI_U16: rc = launch_lds_shifted<uint16_t>(m, (const uint16_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
             case LTMI_I16: rc = launch_lds_shifted<int16_t>(m, (const int16_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
-            case LTMI_F32: rc = launch_lds_shifted<float>(m, (const float *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
+            case LTMI_F32: rc = launch_lds_shifted<float>(m, (const float *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)target, cw * ld_t, acc_t, stream, &handled); break;
             default: break;
         }
         if (rc != LTMI_OK) return rc;
-        if (handled) return LTMI_OK;
+        if (handled) return tile_dtype == LTMI_F32 ? redo_and_deliver() : LTMI_OK;
     }
-    if (m->img64 && tile_dtype != LTMI_C64 && tile_dtype != LTMI_C128 && n_frames < (1ll << 31)) {
+    if (f64_route) {
         bool handled = false;
-        const int rc = shifted64(m, tile, tile_dtype, n_frames, ld_tile, sig_h, sig_w, shifts_host, out,
-                                 ld_out, accumulate, stream, &handled);
+        const int rc = shifted64(m, tile, tile_dtype, n_frames, ld_tile, sig_h, sig_w, shifts_host, target,
+                                 ld_t, acc_t, stream, &handled);
         if (rc != LTMI_OK) return rc;
-        if (handled) return LTMI_OK;
+        if (handled) return redo_and_deliver();
     }
-    // everything else: per-frame kernel with the shifts uploaded to the handle's scratch
-    ShiftCache *c = (ShiftCache *)m->shift_cache;
-    if (!c) {
-        c = new (std::nothrow) ShiftCache();
-        if (!c) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
-        m->shift_cache = c;
-    }
-    const size_t need = (size_t)n_frames * 2;
-    if (c->rows_cap < need) {
-        if (c->rows_dev) LTMI_HIP(hipFree(c->rows_dev));
-        c->rows_dev = nullptr;
-        c->rows_cap = need * 2;
-        LTMI_HIP(hipMalloc((void **)&c->rows_dev, c->rows_cap * sizeof(int32_t)));
-    }
-    c->stage = (c->stage + 1) % ShiftCache::STAGES;
-    c->rows_stage[c->stage].assign(shifts_host, shifts_host + need);
-    LTMI_HIP(hipMemcpyAsync(c->rows_dev, c->rows_stage[c->stage].data(), need * sizeof(int32_t),
-                            hipMemcpyHostToDevice, stream));
-    return ltmi_apply_masks_shifted(m, tile, tile_dtype, n_frames, ld_tile, sig_h, sig_w, c->rows_dev,
+    // everything else: the per-frame kernel, which walks the overlap only
+    const int32_t *shifts_dev = nullptr;
+    const int rc = upload_shifts(m, shifts_host, n_frames, stream, &shifts_dev);
+    if (rc != LTMI_OK) return rc;
+    return ltmi_apply_masks_shifted(m, tile, tile_dtype, n_frames, ld_tile, sig_h, sig_w, shifts_dev,
                                     out, ld_out, accumulate, stream_);
 }
 

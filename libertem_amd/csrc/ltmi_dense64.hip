@@ -55,6 +55,8 @@ template <typename SRC>
 __global__ void k_build_image64_shifted(const SRC *__restrict__ src, double *__restrict__ img,
                                         int64_t n_masks, int64_t n_px, int n_chunks, int cpm, int sig_h,
                                         int sig_w, int dy, int dx) {
+    dy = clamp_shift(dy, sig_h);
+    dx = clamp_shift(dx, sig_w);
     const int64_t total = n_masks * n_px * cpm;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {

@@ -39,6 +39,7 @@ struct NfGuard {
     const void *last_out = nullptr;   // (one-entry cache of out_is_host)
     bool last_out_host = false;
     bool last_checked = false;        // the last guarded product went through k_flag_rows (ltmi_masks_nonfinite_frames)
+    bool via_scratch = false;         // guard_target .. guard_deliver: the product of this call is in `scratch`
 };
 
 struct DenseOrigin {
@@ -235,71 +236,57 @@ static int guard_ensure(ltmi_masks *m, int64_t n_frames, size_t scratch_bytes, h
     return LTMI_OK;
 }
 
-int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, void *out,
-                int64_t ld_out, int accumulate, hipStream_t stream) {
+// Where a guarded product lands: `out` itself, or the device scratch ((n_frames, n_masks), written, not added to).
+// `out += product`: a NaN already in `out` is not this product's; the product is checked on its own.  `out` in host
+// memory (directly written result rows): checked in the device scratch, then copied.  guard_deliver ends the call.
+int guard_target(ltmi_masks *m, int64_t n_frames, void *out, int64_t ld_out, int accumulate, hipStream_t stream,
+                 void **target, int64_t *ld_target) {
     if (n_frames >= (1ll << 31)) LTMI_FAIL(LTMI_E_SHAPE, "ltmi_apply_masks: too many frames in one call");
     const size_t elem = (size_t)dtype_size(m->result_dtype);
     NfGuard *g = nullptr;
     int rc = guard_ensure(m, n_frames, 0, stream, &g);
     if (rc != LTMI_OK) return rc;
-    // `out += product`: a NaN already in `out` is not this product's; the product is checked on its own.  `out` in host
-    // memory (directly written result rows): checked in the device scratch, then copied
-    const bool via_scratch = accumulate || out_is_host(g, out);
-    if (via_scratch) {
+    g->via_scratch = accumulate || out_is_host(g, out);
+    if (g->via_scratch) {
         rc = guard_ensure(m, n_frames, (size_t)n_frames * m->n_masks * elem, stream, &g);
         if (rc != LTMI_OK) return rc;
     }
-    void *target = via_scratch ? g->scratch : out;
-    const int64_t ld_t = via_scratch ? m->n_masks : ld_out;
-    rc = apply_masks_unguarded(m, tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream);
-    if (rc != LTMI_OK) return rc;
-    const bool exact = m->kind == 2 && m->last_exact && !m->dense_origin;   // the gather kernel ran: nothing to check
-    g->last_checked = !exact;
-    if (!exact) {
-        const bool f64 = m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128;
-        const bool cplx = m->result_dtype == LTMI_C64 || m->result_dtype == LTMI_C128;
-        const int n_cols = (int)(m->n_masks * (cplx ? 2 : 1));
-        const int64_t ld_real = ld_t * (cplx ? 2 : 1);
-        LTMI_HIP(hipMemsetAsync(g->ctl, 0, (size_t)(n_frames + 1) * sizeof(int), stream));
-        const dim3 fgrid((unsigned)((n_frames + 3) / 4));
-        if (f64)
-            hipLaunchKernelGGL(k_flag_rows<double>, fgrid, dim3(256), 0, stream, (const double *)target, ld_real,
-                               n_frames, n_cols, g->ctl, g->list);
-        else
-            hipLaunchKernelGGL(k_flag_rows<float>, fgrid, dim3(256), 0, stream, (const float *)target, ld_real,
-                               n_frames, n_cols, g->ctl, g->list);
-        LTMI_HIP(hipGetLastError());
-        if (DenseOrigin *d = (DenseOrigin *)m->dense_origin) {
-            if (tile_dtype != LTMI_F32 || f64)
-                LTMI_FAIL(LTMI_E_DTYPE, "a dense stack held as CSR takes float32 frames and float32 / complex64 results");
-            const float *t = (const float *)tile;
-            if (d->n_unstored > 0) {
-                hipLaunchKernelGGL(k_scan_unstored<float>, dim3((unsigned)n_frames), dim3(256), 0, stream, t, ld_tile,
-                                   n_frames, m->roi_rows, (const int32_t *)d->unstored, d->n_unstored, g->ctl,
-                                   g->list);
-                LTMI_HIP(hipGetLastError());
-            }
-            const size_t lds = (size_t)(m->n_masks + 1) * sizeof(int);
-            const unsigned blocks = (unsigned)std::min<int64_t>(n_frames, 2048);
-            hipLaunchKernelGGL(k_dense_fixup<float>, dim3(blocks), dim3(256), lds, stream, t, ld_tile, m->n_px,
-                               m->roi_rows, (const int32_t *)d->indptr, (const int32_t *)d->indices, (int)m->n_masks,
-                               cplx ? 2 : 1, (float *)target, ld_real, (const int *)g->ctl, (const int32_t *)g->list);
-            LTMI_HIP(hipGetLastError());
-        } else {
-            ltmi_masks *redo = m->sparse_origin ? m->sparse_origin : m;
-            // (the row in bytes is the same for both handles; a complex128 stack's gather image counts float64 columns)
-            const int64_t ld_redo = ld_t * (int64_t)elem / dtype_size(redo->result_dtype);
-            rc = csr_redo(redo, tile, tile_dtype, n_frames, ld_tile, target, ld_redo, g->list, g->ctl, m->roi_rows,
-                          stream);
-            if (rc != LTMI_OK) return rc;
-        }
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
-    }
+    *target = g->via_scratch ? g->scratch : out;
+    *ld_target = g->via_scratch ? m->n_masks : ld_out;
+    return LTMI_OK;
+}
+
+// lists the frames whose result row in `target` holds a non-finite value: *ctl, *list stay on the device
+int guard_list_rows(ltmi_masks *m, const void *target, int64_t ld_target, int64_t n_frames, hipStream_t stream,
+                    int **ctl, int32_t **list) {
+    NfGuard *g = (NfGuard *)m->guard;
+    const bool f64 = m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128;
+    const bool cplx = m->result_dtype == LTMI_C64 || m->result_dtype == LTMI_C128;
+    const int n_cols = (int)(m->n_masks * (cplx ? 2 : 1));
+    const int64_t ld_real = ld_target * (cplx ? 2 : 1);
+    LTMI_HIP(hipMemsetAsync(g->ctl, 0, (size_t)(n_frames + 1) * sizeof(int), stream));
+    const dim3 fgrid((unsigned)((n_frames + 3) / 4));
+    if (f64)
+        hipLaunchKernelGGL(k_flag_rows<double>, fgrid, dim3(256), 0, stream, (const double *)target, ld_real,
+                           n_frames, n_cols, g->ctl, g->list);
+    else
+        hipLaunchKernelGGL(k_flag_rows<float>, fgrid, dim3(256), 0, stream, (const float *)target, ld_real,
+                           n_frames, n_cols, g->ctl, g->list);
+    LTMI_HIP(hipGetLastError());
+    g->last_checked = true;
+    *ctl = g->ctl;
+    *list = g->list;
+    return LTMI_OK;
+}
+
+// the checked product from the scratch to its place (nothing to do when it was computed in place)
+int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, int accumulate, hipStream_t stream) {
+    NfGuard *g = (NfGuard *)m->guard;
+    const size_t elem = (size_t)dtype_size(m->result_dtype);
     if (accumulate)
         return ltmi_add2d(m->device, out, ld_out, g->scratch, m->n_masks, m->result_dtype, n_frames, m->n_masks, 0,
                           (void *)stream);
-    if (via_scratch) {
+    if (g->via_scratch) {
         const int words = (int)(m->n_masks * elem / 4);
         const int64_t total = n_frames * words;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
@@ -308,6 +295,63 @@ int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frame
         LTMI_HIP(hipGetLastError());
     }
     return LTMI_OK;
+}
+
+// shifted masks (ltmi_apply_masks_shifted_host): the routes that multiply whole frames with the zero-filled image of
+// the shifted stack let a non-finite pixel OUTSIDE the overlap reach every mask (0 * NaN), where the reference, which
+// slices frame and masks to the overlap first (udf/masks.py:85-124), never reads it
+bool guard_wanted_shifted(const ltmi_masks *m, int tile_dtype) {
+    if (tile_dtype != LTMI_F32 && tile_dtype != LTMI_F64) return false;
+    return guard_enabled() && (m->result_dtype == LTMI_F32 || m->result_dtype == LTMI_C64 ||
+                               m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128);
+}
+
+int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, void *out,
+                int64_t ld_out, int accumulate, hipStream_t stream) {
+    const size_t elem = (size_t)dtype_size(m->result_dtype);
+    void *target = nullptr;
+    int64_t ld_t = 0;
+    int rc = guard_target(m, n_frames, out, ld_out, accumulate, stream, &target, &ld_t);
+    if (rc != LTMI_OK) return rc;
+    NfGuard *g = (NfGuard *)m->guard;
+    rc = apply_masks_unguarded(m, tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream);
+    if (rc != LTMI_OK) return rc;
+    const bool exact = m->kind == 2 && m->last_exact && !m->dense_origin;   // the gather kernel ran: nothing to check
+    g->last_checked = !exact;
+    if (!exact) {
+        const bool f64 = m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128;
+        const bool cplx = m->result_dtype == LTMI_C64 || m->result_dtype == LTMI_C128;
+        const int64_t ld_real = ld_t * (cplx ? 2 : 1);
+        int *ctl = nullptr;
+        int32_t *list = nullptr;
+        rc = guard_list_rows(m, target, ld_t, n_frames, stream, &ctl, &list);
+        if (rc != LTMI_OK) return rc;
+        if (DenseOrigin *d = (DenseOrigin *)m->dense_origin) {
+            if (tile_dtype != LTMI_F32 || f64)
+                LTMI_FAIL(LTMI_E_DTYPE, "a dense stack held as CSR takes float32 frames and float32 / complex64 results");
+            const float *t = (const float *)tile;
+            if (d->n_unstored > 0) {
+                hipLaunchKernelGGL(k_scan_unstored<float>, dim3((unsigned)n_frames), dim3(256), 0, stream, t, ld_tile,
+                                   n_frames, m->roi_rows, (const int32_t *)d->unstored, d->n_unstored, ctl, list);
+                LTMI_HIP(hipGetLastError());
+            }
+            const size_t lds = (size_t)(m->n_masks + 1) * sizeof(int);
+            const unsigned blocks = (unsigned)std::min<int64_t>(n_frames, 2048);
+            hipLaunchKernelGGL(k_dense_fixup<float>, dim3(blocks), dim3(256), lds, stream, t, ld_tile, m->n_px,
+                               m->roi_rows, (const int32_t *)d->indptr, (const int32_t *)d->indices, (int)m->n_masks,
+                               cplx ? 2 : 1, (float *)target, ld_real, (const int *)ctl, (const int32_t *)list);
+            LTMI_HIP(hipGetLastError());
+        } else {
+            ltmi_masks *redo = m->sparse_origin ? m->sparse_origin : m;
+            // (the row in bytes is the same for both handles; a complex128 stack's gather image counts float64 columns)
+            const int64_t ld_redo = ld_t * (int64_t)elem / dtype_size(redo->result_dtype);
+            rc = csr_redo(redo, tile, tile_dtype, n_frames, ld_tile, target, ld_redo, list, ctl, m->roi_rows, stream);
+            if (rc != LTMI_OK) return rc;
+        }
+        const size_t len = strlen(m->last_kernel);
+        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
+    }
+    return guard_deliver(m, out, ld_out, n_frames, accumulate, stream);
 }
 
 }  // namespace ltmi

@@ -1390,7 +1390,8 @@ def test_scatter_scattered_stack_and_complex(hip, monkeypatch):
 # ---- shifted masks ------------------------------------------------------------------------------------
 def _shift_ref(data3d, masks3d, shifts):
     """out[f, k] = sum over the overlap of frame[f][y, x] * mask_k[y - dy, x - dx] in float64
-    (reference udf/masks.py:85-124 semantics)."""
+    (reference udf/masks.py:85-124 semantics).  Valid for finite frames only: it multiplies the whole frame with a
+    zero-filled shifted stack; the reference that slices the frame is `_slice_ref` in test_shifted_kernels_gpu.py."""
     n, h, w = data3d.shape
     out = np.zeros((n, len(masks3d)), dtype=np.complex128 if np.iscomplexobj(masks3d) else np.float64)
     scale = np.zeros((n, len(masks3d)))
