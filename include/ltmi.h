@@ -315,6 +315,44 @@ int ltmi_host_copy(void *dst, const void *src, int64_t bytes, int threads);
  * the reference's per-partition D2H export of device buffers (src/libertem/common/buffers.py:901-907). */
 int ltmi_host_device_pointer(int device, void *host, void **dev_out);
 
+/* ---- sparse frames (CSR) ---------------------------------------------------------------------
+ * A scan whose frames are stored sparse -- the triple of the reference's RawCSRDataSet
+ * (src/libertem/io/dataset/raw_csr.py:99-132, 410-431): row r of the CSR matrix is frame r, flattened;
+ * `indptr` DEVICE int64 [n_rows + 1] starting at 0, `indices` DEVICE int32 [nnz] (flat pixel numbers),
+ * `data` DEVICE [nnz] of the file's dtype.  The reference hands scipy.sparse tiles of it to the UDFs
+ * (raw_csr.py:481-532); here the triple stays in HBM and the two kernels below read frames out of it.
+ * Both assume CANONICAL rows -- indices strictly ascending, inside [0, n_px) -- which ltmi_csr_check
+ * establishes once: no atomics, plain stores, bitwise repeatable results.  Frames are addressed as
+ * `row0 + i` (rows == NULL) or `rows[i]` (DEVICE int32 list: a region of interest), 0 <= i < n_frames.
+ *
+ * ltmi_csr_check: *flags (DEVICE int, overwritten) = 0 for a canonical triple; bit 0: data that cannot be
+ * used (an index outside [0, n_px), indptr decreasing, not starting at 0 or not ending at nnz -- rows with
+ * a bad indptr are not read); bit 1: a row that is unsorted or stores a pixel twice (scipy's
+ * sum_duplicates() on the host repairs those). */
+int ltmi_csr_check(int device, const int64_t *indptr, const int32_t *indices, int64_t n_rows, int64_t n_px,
+                   int64_t nnz, int *flags, void *stream);
+/* out[i, p] = the dense frame: zero where nothing is stored.  Replaces `tile.toarray()` /
+ * for_backend(tile, NUMPY) of the reference's UDF runner for UDFs that take dense tiles
+ * (src/libertem/udf/base.py:2196-2206).  out: DEVICE (n_frames, n_px) of data_dtype (any 1 / 2 / 4 / 8 byte
+ * dtype: the values are moved, not converted), ld_out >= n_px elements between frames; the elements
+ * [n_px, ld_out) of a row are left as they are. */
+int ltmi_csr_densify(int device, const int64_t *indptr, const int32_t *indices, const void *data,
+                     int data_dtype, const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px,
+                     void *out, int64_t ld_out, void *stream);
+/* out[i, k] (+)= sum over the stored entries e of frame i of data[e] * masks[k, indices[e]]
+ * Replaces ApplyMasksEngine.process_flat on a scipy.sparse CSR tile (`flat_tile @ masks`,
+ * src/libertem/udf/masks.py:59-77) without densifying the frames.  `m`: a handle of
+ * ltmi_masks_create_dense with float32 or float64 results and at most ltmi_csr_max_masks() masks; the
+ * stack is kept a second time pixel-major ([n_px][masks padded to a power of two]), built on the first
+ * call.  data dtypes: uint8, uint16, int16, uint32, int32, float32, converted to the result dtype and
+ * accumulated in it.  A non-finite stored value reaches every mask of its frame (0 * NaN = NaN), as in the
+ * dense product.  *handled = 0 and nothing is done for any other handle or data dtype (then densify and
+ * call ltmi_apply_masks).  ltmi_masks_last_kernel reports "k_apply_csr<...>". */
+int ltmi_apply_masks_csr(ltmi_masks *m, const int64_t *indptr, const int32_t *indices, const void *data,
+                         int data_dtype, const int32_t *rows, int64_t row0, int64_t n_frames, void *out,
+                         int64_t ld_out, int accumulate, void *stream, int *handled);
+int ltmi_csr_max_masks(void);
+
 /* ---- detector corrections -------------------------------------------------------------------
  * Replaces CorrectionSet.apply -> detector.correct on a tile (src/libertem/io/corrections/
  * corrset.py:140-166, detector.py:17-101, called from io/dataset/base/backend.py:121-124) fused

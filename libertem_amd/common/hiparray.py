@@ -327,3 +327,140 @@ class HostMappedArray(HipArray):
 
     def __repr__(self):
         return f"<HostMappedArray shape={self.shape} dtype={self.dtype} ld={self.ld} dev={self._dev}>"
+
+
+class HipCSRArray(HipArray):
+    """
+    Frames of a CSR triple that is resident in HBM -- logical shape (n, *sig), NO dense copy: what a tile of
+    a raw_csr dataset looks like to the kernels that read sparse frames in place (`ltmi_apply_masks_csr`).
+    Everything else calls `materialize()`: the frames densified by `ltmi_csr_densify`.
+    `indptr` (int64, starting at 0), `indices` (int32), `values` (storage dtype of `dtype`): device tensors
+    of the whole triple, rows canonical; the view covers rows [row0, row0 + n), or the rows `rows32` names
+    (device int32: a region of interest).
+    `window`: dict shared by the views of one dataset; its dense buffer is reused by every `materialize()`,
+    so a materialised tile is valid until the next view materialises (None: a fresh buffer per view).
+    """
+    __slots__ = ('_indptr', '_indices', '_values', '_row0', '_rows32', '_mat', '_window', '_nnz')
+    is_csr = True
+
+    def __init__(self, indptr, indices, values, dtype, sig, row0=0, n=None, rows32=None, window=None):
+        n_total = int(indptr.shape[0]) - 1
+        if rows32 is not None:
+            n = int(rows32.shape[0])
+        elif n is None:
+            n = n_total - int(row0)
+        if rows32 is None and not (0 <= int(row0) <= int(row0) + n <= n_total):
+            raise IndexError(f"rows [{row0}, {int(row0) + n}) out of range for {n_total} stored frames")
+        self._t = None
+        self.shape = (int(n),) + tuple(int(s) for s in sig)
+        self.dtype = np.dtype(dtype)
+        self.ld = prod(self.shape[1:])
+        self._indptr, self._indices, self._values = indptr, indices, values
+        self._row0, self._rows32, self._mat, self._window, self._nnz = int(row0), rows32, None, window, None
+
+    @property
+    def device(self):
+        return self._indptr.device.index
+
+    @property
+    def row0(self):
+        return self._row0
+
+    @property
+    def nnz(self):
+        """stored entries of the view's frames (reads `indptr` back: synchronises)"""
+        if self._nnz is None:
+            if self._rows32 is None:
+                ends = self._indptr[[self._row0, self._row0 + self.shape[0]]].cpu()
+                self._nnz = int(ends[1] - ends[0])
+            else:
+                r = self._rows32.long()
+                self._nnz = int((self._indptr[r + 1] - self._indptr[r]).sum().cpu())
+        return self._nnz
+
+    def indptr_ptr(self):
+        return self._indptr.data_ptr()
+
+    def indices_ptr(self):
+        return self._indices.data_ptr()
+
+    def values_ptr(self):
+        return self._values.data_ptr()
+
+    def rows_ptr(self):
+        return 0 if self._rows32 is None else self._rows32.data_ptr()
+
+    def data_ptr(self):
+        raise TypeError("HipCSRArray has no dense data: use materialize() or a sparse-frame kernel")
+
+    @property
+    def torch(self):
+        raise TypeError("HipCSRArray has no dense data: use materialize()")
+
+    @property
+    def is_contiguous(self):
+        return False
+
+    def rows(self, start, stop):
+        start, stop = int(start), int(stop)
+        if not (0 <= start <= stop <= self.shape[0]):
+            raise IndexError(f"rows [{start}, {stop}) out of range for {self.shape}")
+        if self._rows32 is not None:
+            return HipCSRArray(self._indptr, self._indices, self._values, self.dtype, self.shape[1:],
+                               rows32=self._rows32[start:stop], window=self._window)
+        return HipCSRArray(self._indptr, self._indices, self._values, self.dtype, self.shape[1:],
+                           row0=self._row0 + start, n=stop - start, window=self._window)
+
+    def select_rows(self, idx):
+        """the frames idx[i] of this view (host integers, relative to the view) as a row-list view"""
+        torch = _torch()
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if len(idx) and not (0 <= int(idx.min()) and int(idx.max()) < self.shape[0]):
+            raise IndexError(f"frames out of range for {self.shape}")
+        if self._rows32 is not None:
+            sel = self._rows32[torch.from_numpy(idx).to(self._rows32.device)]
+        else:
+            if self._row0 + self.shape[0] > 2 ** 31 - 1:
+                raise ValueError("row lists address at most 2**31 - 1 frames")
+            sel = torch.from_numpy((idx + self._row0).astype(np.int32)).to(self._indptr.device)
+        return HipCSRArray(self._indptr, self._indices, self._values, self.dtype, self.shape[1:],
+                           rows32=sel.contiguous(), window=self._window)
+
+    def reshape(self, shape):
+        return self.materialize().reshape(shape)
+
+    def sig_rows(self, row_start, row_stop):
+        return self.materialize().sig_rows(row_start, row_stop)
+
+    def contiguous(self):
+        return self.materialize()
+
+    def cpu(self):
+        return self.materialize().cpu()
+
+    def fill_(self, value):
+        raise TypeError("HipCSRArray is read-only")
+
+    def materialize(self, stream=None):
+        win = self._window
+        if self._mat is not None and (win is None or win.get('owner') is self):
+            return self._mat
+        from libertem_amd import hip
+        n = self.shape[0]
+        if win is None:
+            out = HipArray.empty(self.shape, self.dtype, self.device)
+        else:
+            buf = win.get('buf')
+            if buf is None or buf.shape[0] < n or buf.dtype != self.dtype:
+                win['buf'] = None                          # (one window at a time)
+                buf = win['buf'] = HipArray.empty((max(n, 1),) + self.shape[1:], self.dtype, self.device)
+            out = buf.rows(0, n)
+            win['owner'] = self
+        if n:
+            hip.csr_densify(self.device, self.indptr_ptr(), self.indices_ptr(), self.values_ptr(), self.dtype,
+                            self.rows_ptr(), self._row0, n, self.ld, out.data_ptr(), out.ld, stream=stream)
+        self._mat = out
+        return out
+
+    def __repr__(self):
+        return f"<HipCSRArray shape={self.shape} dtype={self.dtype} dev={self.device}>"

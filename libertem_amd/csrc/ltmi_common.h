@@ -193,6 +193,8 @@ int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, in
 // ltmi_apply_masks without the guard (ltmi_dense.hip)
 int apply_masks_unguarded(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
                           void *out, int64_t ld_out, int accumulate, hipStream_t stream);
+// sparse frames against a dense stack (ltmi_csrframes.hip): the pixel-major image of the handle
+void csrframes_destroy(ltmi_masks *m);
 int bell_apply(ltmi_masks *m, void *image, int cplx, const void *tile, int tile_dtype,
                int64_t n_frames, int64_t ld_tile, void *out, int64_t ld_out, int accumulate,
                hipStream_t stream, bool *handled);
@@ -246,6 +248,9 @@ struct ltmi_masks {
     const int32_t *roi_rows = nullptr;
     // kind 0 and 1
     void *gmasks = nullptr;  // (n_masks, n_px) of the accumulate type
+    // ltmi_apply_masks_csr: the stack again pixel-major, [n_px][m_pad_px] of float / double, built on first use
+    void *img_px = nullptr;
+    int m_pad_px = 0;
     // kind 2 (ltmi_sparse.hip)
     void *csr = nullptr;
     // kind 0 with more than 64 real columns: the stack again as column blocks of <= 64 columns,

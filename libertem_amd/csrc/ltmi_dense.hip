@@ -1695,6 +1695,7 @@ extern "C" int ltmi_masks_destroy(ltmi_masks *m) {
     ltmi::dense64_destroy(m);
     shift_cache_destroy(m);
     if (m->partials) (void)hipFree(m->partials);
+    ltmi::csrframes_destroy(m);
     if (m->gmasks) (void)hipFree(m->gmasks);
     if (m->csr) (void)ltmi::csr_destroy(m);
     ltmi::guard_destroy(m);

@@ -36,6 +36,7 @@ EXPORTS = (
     'ltmi_logsum_frames',
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
+    'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_masks_set_tuning',
     'ltmi_masks_last_kernel', 'ltmi_comm_unique_id', 'ltmi_comm_create', 'ltmi_comm_destroy',
     'ltmi_comm_all_gather', 'ltmi_comm_all_reduce_sum', 'ltmi_comm_library_info',
@@ -277,6 +278,10 @@ def lib():
         L.ltmi_crystallinity.argtypes = [vp, vp, i32, i64, i64, vp, vp, i32, i32, i32, vp, i32, vp]
         L.ltmi_crystallinity_corrected.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, i32, i32,
                                                    vp, vp, i32, i32, i32, vp, i32, vp]
+        L.ltmi_csr_check.argtypes = [i32, vp, vp, i64, i64, i64, vp, vp]
+        L.ltmi_csr_densify.argtypes = [i32, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, vp]
+        L.ltmi_apply_masks_csr.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, i32, vp, c.POINTER(i32)]
+        L.ltmi_csr_max_masks.argtypes = []
         L.ltmi_masks_set_tuning.argtypes = [vp, i32, i32, i32]
         L.ltmi_masks_last_kernel.argtypes = [vp]
         L.ltmi_comm_unique_id.argtypes = [vp]
@@ -491,29 +496,57 @@ class MaskHandle:
             b.record(st)
             KernelTimer.events.append((a, b, n_frames, self.last_kernel()))
 
+    @staticmethod
+    def _timer_begin(stream):
+        """KernelTimer: the start event of a launch on `stream`, recorded -> (start, stop, stream) | None"""
+        if not KernelTimer.enabled:
+            return None
+        import torch
+        st = torch.cuda.current_stream() if stream is None or isinstance(stream, int) else stream
+        if isinstance(stream, int) and st.cuda_stream != stream:
+            st = torch.cuda.ExternalStream(stream)
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        return a, b, st
+
+    def _timer_end(self, timing, n_frames):
+        if timing is not None:
+            a, b, st = timing
+            b.record(st)
+            KernelTimer.events.append((a, b, n_frames, self.last_kernel()))
+
     def apply_rows(self, tile_ptr, tile_dtype, rows_ptr, n_rows, ld_tile, out_ptr, ld_out, accumulate,
                    stream=None):
         """out[i] (+)= product of frame rows[i] of the tile (rows: device int32).  Returns False --
         nothing done -- when this handle / tile has no row-list kernel (gather the frames instead)."""
         handled = ctypes.c_int(0)
-        if KernelTimer.enabled:
-            import torch
-            st = torch.cuda.current_stream() if stream is None or isinstance(stream, int) \
-                else stream
-            if isinstance(stream, int) and st.cuda_stream != stream:
-                st = torch.cuda.ExternalStream(stream)
-            a = torch.cuda.Event(enable_timing=True)
-            b = torch.cuda.Event(enable_timing=True)
-            a.record(st)
+        timing = self._timer_begin(stream)
         check(lib().ltmi_apply_masks_rows(
             self._ptr, ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), ctypes.c_void_p(rows_ptr),
             int(n_rows), int(ld_tile), ctypes.c_void_p(out_ptr), int(ld_out) * self._out_words,
             1 if accumulate else 0,
             stream if isinstance(stream, int) else _stream_ptr(stream), ctypes.byref(handled)),
             'ltmi_apply_masks_rows')
-        if KernelTimer.enabled and handled.value:
-            b.record(st)
-            KernelTimer.events.append((a, b, n_rows, self.last_kernel()))
+        if handled.value:
+            self._timer_end(timing, n_rows)
+        return bool(handled.value)
+
+    def apply_csr(self, indptr_ptr, indices_ptr, data_ptr, data_dtype, rows_ptr, row0, n_frames, out_ptr,
+                  ld_out, accumulate, stream=None):
+        """out[i] (+)= product of the sparse frame row0 + i (or rows[i]: device int32) of a CSR triple in HBM
+        with this dense stack, stored entries only (ltmi_apply_masks_csr).  Returns False -- nothing done --
+        when the handle or the data dtype has no such kernel (densify the frames instead)."""
+        handled = ctypes.c_int(0)
+        timing = self._timer_begin(stream)
+        check(lib().ltmi_apply_masks_csr(
+            self._ptr, ctypes.c_void_p(indptr_ptr), ctypes.c_void_p(indices_ptr), ctypes.c_void_p(data_ptr),
+            dtype_code(data_dtype), ctypes.c_void_p(rows_ptr or None), int(row0), int(n_frames),
+            ctypes.c_void_p(out_ptr), int(ld_out), 1 if accumulate else 0,
+            stream if isinstance(stream, int) else _stream_ptr(stream), ctypes.byref(handled)),
+            'ltmi_apply_masks_csr')
+        if handled.value:
+            self._timer_end(timing, n_frames)
         return bool(handled.value)
 
     def apply_shifted(self, tile_ptr, tile_dtype, n_frames, ld_tile, sig_h, sig_w, shifts_ptr,
@@ -545,6 +578,34 @@ class MaskHandle:
             self.close()
         except Exception:
             pass
+
+
+def csr_max_masks():
+    """the largest stack ltmi_apply_masks_csr multiplies with sparse frames"""
+    return int(lib().ltmi_csr_max_masks())
+
+
+def csr_check(device, indptr_ptr, indices_ptr, n_rows, n_px, nnz, stream=None):
+    """-> flags of a CSR triple in HBM (synchronises): 0 canonical, bit 0: unusable (index out of range,
+    broken indptr), bit 1: rows unsorted or with duplicates"""
+    import torch
+    flags = torch.zeros(1, dtype=torch.int32, device=f'cuda:{int(device)}')
+    check(lib().ltmi_csr_check(int(device), ctypes.c_void_p(indptr_ptr), ctypes.c_void_p(indices_ptr or None),
+                               int(n_rows), int(n_px), int(nnz), ctypes.c_void_p(flags.data_ptr()),
+                               _stream_ptr(stream)), 'ltmi_csr_check')
+    if stream is not None:
+        torch.cuda.synchronize(int(device))
+    return int(flags.cpu()[0])
+
+
+def csr_densify(device, indptr_ptr, indices_ptr, data_ptr, data_dtype, rows_ptr, row0, n_frames, n_px,
+                out_ptr, ld_out, stream=None):
+    """out[i, :n_px] = the dense frame row0 + i (or rows[i]: device int32) of a CSR triple in HBM"""
+    check(lib().ltmi_csr_densify(
+        int(device), ctypes.c_void_p(indptr_ptr), ctypes.c_void_p(indices_ptr or None),
+        ctypes.c_void_p(data_ptr or None), dtype_code(data_dtype), ctypes.c_void_p(rows_ptr or None), int(row0),
+        int(n_frames), int(n_px), ctypes.c_void_p(out_ptr), int(ld_out),
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_csr_densify')
 
 
 def sum_frames_workspace(n_frames, n_px, out_dtype):

@@ -832,7 +832,11 @@ class MemPartition(Partition):
                 idxs = idxs - self._local0 + row0           # rows of `flat`
             if flat.device != device:
                 raise RuntimeError(f"dataset lives on GPU {flat.device}, worker drives GPU {device}")
-            if idxs is not None and corrections is None and \
+            if idxs is not None and hasattr(flat, 'select_rows'):
+                # sparse frames: the ROI is a row list over the CSR triple
+                flat = flat.select_rows(idxs)
+                base = 0
+            elif idxs is not None and corrections is None and \
                     int(idxs.max()) < 2 ** 31 - 1 and flat.is_contiguous:
                 # the frames the ROI selects as a ROW LIST over the resident array: the mask kernels
                 # read them in place (ltmi_apply_masks_rows), other consumers gather on demand

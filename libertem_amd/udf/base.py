@@ -573,6 +573,10 @@ class UDF(UDFBase):
     #: over the resident array) -- other UDFs are handed the gathered frames.
     ACCEPTS_ROW_VIEWS = False
 
+    #: True: `process_tile` accepts a `HipCSRArray` (sparse frames of a raw_csr dataset as a view of the
+    #: CSR triple in HBM) -- other UDFs are handed the densified frames.
+    ACCEPTS_CSR_VIEWS = False
+
     #: True: `process_tile` is handed whole frames -- the negotiator takes the full signal shape as the
     #: base shape, as it does for `process_frame` / `process_partition` UDFs.  A tileshape forced on the
     #: dataset still wins; such UDFs check `meta.sig_sliced_tiles` themselves.
@@ -1069,9 +1073,11 @@ class UDFPartRunner:
     def _run_tile(self, udf, method, partition, tile):
         data = tile.data
         if hasattr(data, 'materialize') and not (
-                method == UDFMethod.TILE and getattr(udf, 'ACCEPTS_ROW_VIEWS', False)):
-            # a region of interest as a row list over the resident frames: only the mask operators
-            # read through it, everyone else gets the gathered frames (gathered once per tile)
+                method == UDFMethod.TILE and getattr(
+                    udf, 'ACCEPTS_CSR_VIEWS' if getattr(data, 'is_csr', False) else 'ACCEPTS_ROW_VIEWS', False)):
+            # a region of interest as a row list over the resident frames, or sparse frames as a view of
+            # their CSR triple: only the mask operators read through it, everyone else gets the gathered /
+            # densified frames (once per tile)
             data = data.materialize()
         if method == UDFMethod.TILE:
             udf.set_contiguous_views_for_tile(partition, tile)
@@ -1260,6 +1266,9 @@ class UDFRunner:
 
     def _plan_run(self, dataset, executor, roi, corrections, backends, dry):
         self._check_preconditions(dataset, roi)
+        if corrections is not None and corrections.have_corrections() \
+                and not getattr(dataset, 'supports_correction', lambda: True)():
+            raise NotImplementedError(f"corrections are not implemented for {type(dataset).__name__}")
         backends = _canonical_backends(backends)
         device_class = executor.device_class
         chosen = _execution_plan(self._udfs, dataset.array_backends, device_class,

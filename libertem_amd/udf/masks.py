@@ -18,7 +18,7 @@ from libertem_amd.common.math import prod
 from libertem_amd.common.udf import UDFMethod
 from libertem_amd.common.container import MaskContainer
 from libertem_amd.common.buffers import AuxBufferWrapper
-from libertem_amd.common.hiparray import HipArray, HipRowsArray
+from libertem_amd.common.hiparray import HipArray, HipRowsArray, HipCSRArray
 from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.common.fingerprint import fingerprint, is_opaque
 from libertem_amd.udf.base import UDF
@@ -66,6 +66,12 @@ def _cached_container(mask_factories, dtype, use_sparse, count, default_sparse, 
         # (MaskHandle.__del__)
         _CONTAINER_CACHE.popitem(last=False)
     return container
+
+
+#: Sparse frames (tiles of a raw_csr dataset) are multiplied in place -- stored entries only, no dense copy of
+#: the frames -- with real floating stacks that are held dense, of at most this many masks (what the pixel-major
+#: image of `ltmi_apply_masks_csr` takes); larger stacks get the densified frames and the matrix-core kernels.
+CSR_DIRECT_MAX_MASKS = 64
 
 
 #: fold detector corrections into the mask stack of dense ApplyMasksUDF runs (see
@@ -251,6 +257,23 @@ class ApplyMasksEngine:
             raise HipRequiredError("ApplyMasksEngine.process_tile expects a device tile (HipArray)")
         n = tile.shape[0]
         n_px = prod(tile.shape[1:])
+        if isinstance(tile, HipCSRArray):
+            # sparse frames as a view of their CSR triple: a real floating stack held dense multiplies the
+            # stored entries in place; every other stack gets the frames densified
+            # (an integer stack gives a float result with float32 input -- float32 x int32 is float64 -- and
+            # still takes the dense route, as every exact-integer stack does; boolean masks are held as floats)
+            if out is not None and self._const is None and self.masks.use_sparse is False \
+                    and np.dtype(self.masks.dtype).kind in 'fb' \
+                    and self.result_dtype in (np.dtype(np.float32), np.dtype(np.float64)) \
+                    and len(self.masks) <= CSR_DIRECT_MAX_MASKS:
+                handle = self._get_handle(tile.dtype)
+                if handle.n_px == n_px and out.shape[0] == n and \
+                        prod(out.shape[1:]) == handle.n_masks and \
+                        handle.apply_csr(tile.indptr_ptr(), tile.indices_ptr(), tile.values_ptr(), tile.dtype,
+                                         tile.rows_ptr(), tile.row0, n, out.data_ptr(), out.ld, accumulate,
+                                         stream=self.stream_ptr):
+                    return out
+            tile = tile.materialize(stream=self.stream_ptr)
         if isinstance(tile, HipRowsArray):
             # a region of interest as a row list over the resident frames: the dense float32 kernels
             # read the selected frames in place; anything else gets them gathered
@@ -309,7 +332,7 @@ class ApplyMasksEngine:
         import torch
         if not isinstance(tile, HipArray):
             raise HipRequiredError("process_tile_shifted expects a device tile (HipArray)")
-        if isinstance(tile, HipRowsArray):
+        if isinstance(tile, (HipRowsArray, HipCSRArray)):
             tile = tile.materialize(stream=self.stream_ptr)
         sig = tuple(self.meta.dataset_shape.sig)
         if len(sig) != 2 or tuple(tile.shape[1:]) != sig:
@@ -353,6 +376,7 @@ class ApplyMasksUDF(UDF):
 
     REUSE_TASK_INSTANCES = True      # (udf/base.py: per-partition instances kept between runs)
     ACCEPTS_ROW_VIEWS = True         # process_tile reads an ROI's frames through a row list (no gather)
+    ACCEPTS_CSR_VIEWS = True         # ... and sparse frames through their CSR triple (no dense copy)
 
     def __init__(self, mask_factories, use_torch=True, use_sparse=None, mask_count=None,
                  mask_dtype=None, preferred_dtype=None, backends=None, shifts=None, cache=True, **kwargs):
