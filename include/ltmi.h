@@ -390,6 +390,14 @@ int ltmi_byteswap(int device, const void *src, void *dst, int itemsize, int64_t 
 int ltmi_mib_decode(int device, const void *src, int64_t frame_stride, int64_t header_bytes, int kind,
                     int bits, int quad, int64_t n_frames, int height, int width, void *dst,
                     int dst_dtype, void *stream);
+/* Which of the two decode kernels the calling thread's last ltmi_mib_decode launched, e.g.
+ * "k_mib_decode16<u16>" (16 bytes of output per thread: payloads of whole 16-byte chunks),
+ * "k_mib_decode<r12,quad>" (one 64-bit word per thread: every other shape, and every shape while
+ * LTMI_MIB_WORDS is set in the environment, which is read on every call), "k_mib_decode16<r24f>" (24 bit
+ * into LTMI_F32).  "" before the first decode; a call that fails its argument checks or has n_frames == 0
+ * launches nothing and leaves the string as it was.  Thread-local storage: valid until the thread's next
+ * decode. */
+const char *ltmi_mib_last_kernel(void);
 
 /* Centre-of-mass post-processing on a 2D scan of ny x nx positions: from the rows (sum, sum*y, sum*x)
  * of the 3-mask product to the shift field and its derived maps, float64.  Replaces the NumPy chain

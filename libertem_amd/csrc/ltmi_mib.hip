@@ -191,7 +191,26 @@ k_mib_decode16(const unsigned char *__restrict__ src, int64_t frame_stride, unsi
     *(u64x2_u *)(frame_out + px0 * OUT) = o;
 }
 
+// the kernel of the last launch issued by this thread ("" before the first): ltmi_mib_last_kernel
+thread_local char t_last_kernel[48] = {0};
+
+void note_kernel(const char *kernel, int mode, bool quad) {
+    static const char *const names[] = {"u8", "u16", "u32", "r1", "r6", "r12", "r24", "r24f"};
+    snprintf(t_last_kernel, sizeof(t_last_kernel), "%s<%s%s>", kernel, names[mode], quad ? ",quad" : "");
+}
+
+// k_mib_decode16 (16 bytes of output per thread) when the shape allows: the payload in whole 16-byte chunks
+// (1-bit words always: 64 bytes of output each), quad rows of 6 / 12 bit in whole chunks per chip row.
+// LTMI_MIB_WORDS in the environment (read per call: tests select the kernel in-process): always k_mib_decode.
+bool mib_wide(int mode, bool quad, int64_t payload, int width, int out_size) {
+    if (getenv("LTMI_MIB_WORDS") != nullptr) return false;
+    const int ppc = 16 / out_size;
+    return (payload % 16 == 0 || mode == M_R1) && (!quad || mode == M_R1 || ((width / 2) % ppc == 0));
+}
+
 }  // namespace
+
+extern "C" const char *ltmi_mib_last_kernel(void) { return t_last_kernel; }
 
 extern "C" int ltmi_mib_decode(int device, const void *src, int64_t frame_stride, int64_t header_bytes,
                                int kind, int bits, int quad, int64_t n_frames, int height, int width,
@@ -241,12 +260,7 @@ extern "C" int ltmi_mib_decode(int device, const void *src, int64_t frame_stride
     }
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-    // 16 bytes of output per thread when the shape allows (env LTMI_MIB_WORDS=1: the per-word kernel)
-    static const bool words_only = getenv("LTMI_MIB_WORDS") != nullptr;
-    const int ppc = 16 / ltmi::dtype_size(want);
-    const bool wide = !words_only && (payload % 16 == 0 || mode == M_R1) &&
-                      (!quad || mode == M_R1 || ((width / 2) % ppc == 0));
-    if (wide) {
+    if (mib_wide(mode, quad != 0, payload, width, (int)ltmi::dtype_size(want))) {
         const int64_t chunks = mode == M_R1 ? payload / 2 : (mode == M_R24 || mode == M_R24F) ? payload / 16
                                                                                              : payload / 16;
         if (chunks > (1ll << 30)) LTMI_FAIL(LTMI_E_SHAPE, "ltmi_mib_decode: frame too large");
@@ -273,6 +287,7 @@ extern "C" int ltmi_mib_decode(int device, const void *src, int64_t frame_stride
                 default: LTMI_MIB_LAUNCH16(M_R24F, false); break;
             }
 #undef LTMI_MIB_LAUNCH16
+            note_kernel("k_mib_decode16", mode, quad != 0);
             LTMI_HIP(hipGetLastError());
         }
         return LTMI_OK;
@@ -302,6 +317,7 @@ extern "C" int ltmi_mib_decode(int device, const void *src, int64_t frame_stride
             default: LTMI_MIB_LAUNCH(M_R24F, false); break;
         }
 #undef LTMI_MIB_LAUNCH
+        note_kernel("k_mib_decode", mode, quad != 0);
         LTMI_HIP(hipGetLastError());
     }
     return LTMI_OK;

@@ -34,7 +34,7 @@ EXPORTS = (
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
     'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
     'ltmi_logsum_frames',
-    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
+    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_masks_set_tuning',
@@ -271,6 +271,8 @@ def lib():
         L.ltmi_repair_pixels.argtypes = [i32, vp, i32, i64, i64, vp, vp, vp, i32, i32, vp]
         L.ltmi_byteswap.argtypes = [i32, vp, vp, i32, i64, vp]
         L.ltmi_mib_decode.argtypes = [i32, vp, i64, i64, i32, i32, i32, i64, i32, i32, vp, i32, vp]
+        L.ltmi_mib_last_kernel.argtypes = []
+        L.ltmi_mib_last_kernel.restype = c.c_char_p
         L.ltmi_com_fields.argtypes = [i32, vp, i64, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp,
                                       vp, vp, vp, vp, vp]
         L.ltmi_fft_plan_create.argtypes = [i32, i32, i32, i32, c.POINTER(vp)]
@@ -763,6 +765,12 @@ def mib_decode(device, src_ptr, frame_stride, header_bytes, kind, bits, quad, n_
         int(device), src_ptr, int(frame_stride), int(header_bytes), ord(kind), int(bits), int(bool(quad)),
         int(n_frames), int(height), int(width), dst_ptr, dtype_code(dst_dtype),
         stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_mib_decode')
+
+
+def mib_last_kernel():
+    """Name of the kernel this thread's last `mib_decode` launched, e.g. 'k_mib_decode16<u16>' or
+    'k_mib_decode<r12,quad>'; '' before the first decode."""
+    return lib().ltmi_mib_last_kernel().decode()
 
 
 def com_fields(device, raw_ptr, ld_raw, ny, nx, ref_y, ref_x, transform, out_y, out_x, out_mag=None,
