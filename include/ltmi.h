@@ -399,6 +399,19 @@ int ltmi_mib_decode(int device, const void *src, int64_t frame_stride, int64_t h
  * decode. */
 const char *ltmi_mib_last_kernel(void);
 
+/* Gatan K2 IS sector files decoded on the device.  `sector_src`: HOST array of 8 DEVICE pointers, one per
+ * sector file (`*_1.bin` ... `*_8.bin`); pointer s is at the first block of the first frame of sector s in the
+ * uploaded file bytes, frame f of the sector at sector_src[s] + f * 32 * 0x5758 (32 blocks of a 40-byte header
+ * + 930 rows x 16 pixels, 12 bit little-endian: a = b0 | (b1 & 0x0F) << 8, b = b1 >> 4 | b2 << 4).  The 8
+ * pointers are independent (the sectors need not start at the same file offset); each is a multiple of 8
+ * bytes, which every block and payload row then is too.  Block k of a frame covers the rows
+ * [930 (k / 16), +930) and the frame columns [256 s + 16 (15 - k % 16), +16).  dst: (n_frames, 1860, 2048)
+ * contiguous, 16-byte aligned, `dst_dtype` must be LTMI_U16.  n_frames == 0 launches nothing.  Replaces
+ * K2ISDecoder's decode_k2is / decode_uint12_le and the per-block read ranges that feed them
+ * (src/libertem/io/dataset/k2is.py:82-164, 172-231), which the reference runs on the host per tile. */
+int ltmi_k2is_decode(int device, const void *const sector_src[8], int64_t n_frames, void *dst,
+                     int dst_dtype, void *stream);
+
 /* Centre-of-mass post-processing on a 2D scan of ny x nx positions: from the rows (sum, sum*y, sum*x)
  * of the 3-mask product to the shift field and its derived maps, float64.  Replaces the NumPy chain
  * center_shifts -> apply_correction -> magnitude / divergence / curl_2d of src/libertem/udf/com.py:

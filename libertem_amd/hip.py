@@ -34,7 +34,7 @@ EXPORTS = (
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
     'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
     'ltmi_logsum_frames',
-    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
+    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_masks_set_tuning',
@@ -272,6 +272,7 @@ def lib():
         L.ltmi_byteswap.argtypes = [i32, vp, vp, i32, i64, vp]
         L.ltmi_mib_decode.argtypes = [i32, vp, i64, i64, i32, i32, i32, i64, i32, i32, vp, i32, vp]
         L.ltmi_mib_last_kernel.argtypes = []
+        L.ltmi_k2is_decode.argtypes = [i32, vp, i64, vp, i32, vp]
         L.ltmi_mib_last_kernel.restype = c.c_char_p
         L.ltmi_com_fields.argtypes = [i32, vp, i64, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp,
                                       vp, vp, vp, vp, vp]
@@ -771,6 +772,20 @@ def mib_last_kernel():
     """Name of the kernel this thread's last `mib_decode` launched, e.g. 'k_mib_decode16<u16>' or
     'k_mib_decode<r12,quad>'; '' before the first decode."""
     return lib().ltmi_mib_last_kernel().decode()
+
+
+def k2is_decode(device, sector_ptrs, n_frames, dst_ptr, dst_dtype=np.uint16, stream=None):
+    """Frames of a K2IS acquisition (device copies of the bytes of the 8 sector files; `sector_ptrs`: the 8
+    device addresses of the first block of the first frame) -> (n_frames, 1860, 2048) uint16.  `sector_ptrs`
+    None stands for a null array (argument checks)."""
+    arr = None
+    if sector_ptrs is not None:
+        if len(sector_ptrs) != 8:
+            raise ValueError(f"a K2IS acquisition has 8 sectors, not {len(sector_ptrs)}")
+        arr = (ctypes.c_void_p * 8)(*[int(p) if p else None for p in sector_ptrs])
+    check(lib().ltmi_k2is_decode(
+        int(device), arr, int(n_frames), dst_ptr, dtype_code(dst_dtype),
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_k2is_decode')
 
 
 def com_fields(device, raw_ptr, ld_raw, ny, nx, ref_y, ref_x, transform, out_y, out_x, out_mag=None,
