@@ -412,6 +412,24 @@ const char *ltmi_mib_last_kernel(void);
 int ltmi_k2is_decode(int device, const void *const sector_src[8], int64_t n_frames, void *dst,
                      int dst_dtype, void *stream);
 
+/* PNDetector pnCCD .frms6 frames unfolded on the device.  `src`: DEVICE address of the first frame's payload in
+ * a copy of (part of) a .frms6 file; the payload of frame f is at src + f * frame_stride (in a file: 64-byte
+ * frame header + payload, so frame_stride = 64 + height * width * 2): `height` rows of `width` little-endian
+ * uint16, folded.  With x = width / 2 the output frame is (2 * height * binning, x): output row y, binned index
+ * yb = y / binning, is raw row yb, columns [0, x), in order for yb < height, and raw row 2 * height - 1 - yb,
+ * columns [x, 2 x), reversed otherwise; binned rows are repeated, not rescaled.  dst: (n_frames,
+ * 2 * height * binning, x) contiguous, `dst_dtype` must be LTMI_U16.  `width` is even, `binning` 1, 2 or 4, src and
+ * frame_stride multiples of 2, height and width at most 65535.  Half rows of whole 16-byte pieces (x % 8 == 0)
+ * with src, frame_stride and dst multiples of 16 take the kernel with 16-byte loads and stores, every other
+ * geometry the one with a pixel per lane: chosen here, on the host.  n_frames == 0 (or an empty frame) launches
+ * nothing.  Replaces the per-row read ranges and FRMS6Decoder's row-by-row decoders
+ * (src/libertem/io/dataset/frms6.py:232-366), which the reference runs on the host per tile. */
+int ltmi_frms6_decode(int device, const void *src, int64_t frame_stride, int64_t n_frames, int height,
+                      int width, int binning, void *dst, int dst_dtype, void *stream);
+/* Which kernel the calling thread's last ltmi_frms6_decode launched: "k_frms6_unfold16" or "k_frms6_unfold2";
+ * "" before the first.  A call that launches nothing leaves the string as it was. */
+const char *ltmi_frms6_last_kernel(void);
+
 /* Centre-of-mass post-processing on a 2D scan of ny x nx positions: from the rows (sum, sum*y, sum*x)
  * of the 3-mask product to the shift field and its derived maps, float64.  Replaces the NumPy chain
  * center_shifts -> apply_correction -> magnitude / divergence / curl_2d of src/libertem/udf/com.py:

@@ -194,6 +194,7 @@ class Context:
             raise ValueError("result_where must be None, 'host' or 'device'")
         if result_where == 'device' and not hasattr(self.executor, '_merge_on_device'):
             raise NotImplementedError("result_where='device' needs the HIP executor")
+        corrections = self._corrections_for(dataset, corrections)
         if corrections is not None and not corrections.have_corrections():
             corrections = None
         udf_is_list = isinstance(udf, (tuple, list))
@@ -212,6 +213,16 @@ class Context:
                                          **({'result_where': 'device'} if result_where == 'device' else {}))
         buffers = res.buffers
         return tuple(buffers) if udf_is_list else buffers[0]
+
+    @staticmethod
+    def _corrections_for(dataset, corrections):
+        """the corrections a dataset brings along (FRMS6: dark frame and gain map) apply when the caller passes
+        none (reference api.py `run_udf` / `run_udf_iter` / `map`); an explicit set, an empty one included, wins.
+        Every entry point ends here: `run`, `map` and the async twins call `run_udf` / `run_udf_iter`, a nested run
+        resolves on the sibling context."""
+        if corrections is None and hasattr(dataset, 'get_correction_data'):
+            corrections = dataset.get_correction_data()
+        return corrections
 
     def _nested_context(self):
         """The reference runs UDFs from inside a `run_udf_iter` loop (tests/test_context.py test_udf_iter: a second run
@@ -303,6 +314,7 @@ class Context:
         if roi is not None:
             roi = self._normalize_roi(roi, dataset)
         runner = UDFRunner(udfs)
+        corrections = self._corrections_for(dataset, corrections)
         if corrections is not None and not corrections.have_corrections():
             corrections = None
         # the executor's gate is held from the first step to the end of the iteration (or close()): partial

@@ -34,7 +34,7 @@ EXPORTS = (
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
     'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
     'ltmi_logsum_frames',
-    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_com_fields', 'ltmi_fft_plan_create',
+    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_masks_set_tuning',
@@ -273,6 +273,9 @@ def lib():
         L.ltmi_mib_decode.argtypes = [i32, vp, i64, i64, i32, i32, i32, i64, i32, i32, vp, i32, vp]
         L.ltmi_mib_last_kernel.argtypes = []
         L.ltmi_k2is_decode.argtypes = [i32, vp, i64, vp, i32, vp]
+        L.ltmi_frms6_decode.argtypes = [i32, vp, i64, i64, i32, i32, i32, vp, i32, vp]
+        L.ltmi_frms6_last_kernel.argtypes = []
+        L.ltmi_frms6_last_kernel.restype = c.c_char_p
         L.ltmi_mib_last_kernel.restype = c.c_char_p
         L.ltmi_com_fields.argtypes = [i32, vp, i64, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp,
                                       vp, vp, vp, vp, vp]
@@ -786,6 +789,23 @@ def k2is_decode(device, sector_ptrs, n_frames, dst_ptr, dst_dtype=np.uint16, str
     check(lib().ltmi_k2is_decode(
         int(device), arr, int(n_frames), dst_ptr, dtype_code(dst_dtype),
         stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_k2is_decode')
+
+
+def frms6_decode(device, src_ptr, frame_stride, n_frames, height, width, binning, dst_ptr,
+                 dst_dtype=np.uint16, stream=None):
+    """Folded frames of a .frms6 file (device copy of the file bytes; `src_ptr`: the first frame's payload,
+    the next ones `frame_stride` bytes apart; `height` x `width` raw) -> (n_frames, 2 * height * binning,
+    width // 2) uint16."""
+    check(lib().ltmi_frms6_decode(
+        int(device), src_ptr, int(frame_stride), int(n_frames), int(height), int(width), int(binning),
+        dst_ptr, dtype_code(dst_dtype), stream if isinstance(stream, int) else _stream_ptr(stream)),
+        'ltmi_frms6_decode')
+
+
+def frms6_last_kernel():
+    """Name of the kernel this thread's last `frms6_decode` launched: 'k_frms6_unfold16' (16-byte loads and
+    stores) or 'k_frms6_unfold2' (a pixel per lane); '' before the first."""
+    return lib().ltmi_frms6_last_kernel().decode()
 
 
 def com_fields(device, raw_ptr, ld_raw, ny, nx, ref_y, ref_x, transform, out_y, out_x, out_mag=None,

@@ -726,8 +726,11 @@ class MemPartition(Partition):
             compressed_origin = self.slice.adjust_for_roi(roi).origin[0]
         # scan positions a `sync_offset` leaves without a frame -- before the first or after the last one -- are NOT
         # delivered (reference base/partition.py read ranges; tests/udf/test_coords.py): host UDFs see frames that
-        # exist, their result rows elsewhere keep their initial value.  (The device path multiplies the zero frames
-        # that stand there: the same sums for every native operator, and write-once result rows stay defined.)
+        # exist, their result rows elsewhere keep their initial value.  (The device path delivers the zero frames
+        # that stand there: the same sums for every native operator, and write-once result rows stay defined.
+        # A UDF for which they are not the same -- `VALID_FRAMES_ONLY`, or any UDF once a dark frame is subtracted
+        # -- has them trimmed off its tiles and gets zero-filled buffers instead of write-once ones: udf/base.py
+        # `_skips_frameless`.)
         first, last = 0, n
         valid = getattr(self._ds, '_valid_frames', None)
         if valid is not None:

@@ -297,7 +297,8 @@ class MIBDataSet(MemoryDataSet):
                 num_partitions=self._num_partitions_arg, shard=self._shard_arg)
         self._sync_offset = so
         # scan positions that hold a frame of the series (global positions; frame g sits at g - so): the rest are
-        # the zero frames decoded above, which UDFs with `VALID_FRAMES_ONLY` are not handed
+        # the zero frames decoded above, which UDFs with `VALID_FRAMES_ONLY` -- and, under a dark frame, all UDFs --
+        # are not handed (udf/base.py `_skips_frameless`)
         lo = min(n_nav, max(0, -so))
         hi = max(lo, min(n_nav, self._image_count - so))
         self._valid_frames = None if (lo, hi) == (0, n_nav) else (lo, hi)

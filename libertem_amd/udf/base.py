@@ -391,6 +391,9 @@ class UDFBase(UDFProtocol):
         """target: callable(name, buffer, shape, dtype) -> HipArray | None of the executor: where
         the rows of a write-once nav buffer of THIS partition may be written directly."""
         once = self.get_write_once_buffers() if self._backend == HIP else ()
+        if once and _skips_frameless(self, partition, getattr(self.meta, 'corrections', None)):
+            # result rows of scan positions without a frame are never written: they keep the zero fill
+            once = ()
         for ns in [self.results]:
             ns.allocate_for_part(partition, roi, lib=self.xp, write_once=once, target=target)
 
@@ -849,6 +852,19 @@ def _valid_compressed_range(partition, roi):
     return lo, hi
 
 
+def _skips_frameless(udf, partition, corrections):
+    """True: `udf` is not handed the scan positions of the partition's dataset that hold no frame (the zero frames
+    the device path delivers there; host tiles skip them already).  That is a UDF that sets `VALID_FRAMES_ONLY`,
+    and with a dark frame every UDF: a zero frame minus the dark frame is not zero (FRMS6 sets bring a dark frame
+    along with any sync_offset).  Its result rows there keep their initial value, so none of its buffers is
+    write-once (`UDFBase.allocate_for_part`)."""
+    if getattr(getattr(partition, '_ds', None), '_valid_frames', None) is None:
+        return False
+    if getattr(udf, 'VALID_FRAMES_ONLY', False):
+        return True
+    return corrections is not None and getattr(corrections, 'get_dark_frame', lambda: None)() is not None
+
+
 def _trim_tile(tile, valid):
     """the frames of `tile` inside the nav range `valid`, as a tile (the same one if all are); None: no frame"""
     from libertem_amd.io.dataset.base import DataTile
@@ -1039,14 +1055,14 @@ class UDFPartRunner:
                          and udf.results.get_buffer(k).kind == 'nav']
                 if names:
                     sinkable.append((i, udf, names))
-        # positions a sync_offset left without a frame, for UDFs that must not see the zero frames the device path
-        # delivers there (`VALID_FRAMES_ONLY`; host tiles skip them already)
-        valid = _valid_compressed_range(partition, params.roi) \
-            if any(getattr(u, 'VALID_FRAMES_ONLY', False) for u in self._udfs) else None
+        # positions a sync_offset left without a frame, for the UDFs that must not see the zero frames the device
+        # path delivers there (`_skips_frameless`)
+        skips = [_skips_frameless(udf, partition, params.corrections) for udf in self._udfs]
+        valid = _valid_compressed_range(partition, params.roi) if any(skips) else None
         for tile in tiles:
-            for udf, method in zip(self._udfs, methods):
+            for udf, method, skip in zip(self._udfs, methods, skips):
                 try:
-                    if valid is not None and getattr(udf, 'VALID_FRAMES_ONLY', False):
+                    if valid is not None and skip:
                         vt = _trim_tile(tile, valid)
                         if vt is not None:
                             self._run_tile(udf, method, partition, vt)

@@ -71,6 +71,7 @@ class StdDevUDF(UDF):
     REUSE_TASK_INSTANCES = True      # (frame counters restart in preprocess)
     #: positions a sync_offset leaves without a frame are not delivered on the device either: zero
     #: frames there would change the mean, the variance and the frame count
+    #: (udf/base.py `_skips_frameless`; under a dark frame that holds for every UDF, flag or not)
     VALID_FRAMES_ONLY = True
 
     def __init__(self, dtype=None, use_numba=True):
