@@ -9,8 +9,8 @@ half; binned readouts store one row for `bin` detector rows.
 The host reads headers only.  Where the reference builds one read range per detector row and unfolds row by
 row under numba for every tile (frms6.py:232-366), `initialize()` streams the frame records ONCE through pinned
 bounce buffers into HBM, `ltmi_frms6_decode` (csrc/ltmi_frms6.hip) unfolds them behind each copy, and the
-dataset is a device-resident uint16 array from then on.  A scan that does not fit is STREAMED per partition, as
-for .mib files (mib.py).
+dataset is a device-resident uint16 array from then on.  A scan that does not fit is STREAMED per partition
+(decoded.py).
 
 Corrections: the dark frame is the mean of the frames of file 000, decoded by the same kernel and summed on the
 device in exact integers (`ltmi_sum_frames`, int64), then converted to float32 and divided once by the frame
@@ -31,7 +31,7 @@ from libertem_amd.common.math import prod
 from libertem_amd.common.hiparray import HipArray
 from .base import DataSetException, DataSetMeta
 from .memory import MemoryDataSet
-from .mib import MIBDataSet, _bounce_buffers
+from .decoded import DecodedFileDataSet, FrameLayout, _host_copy
 
 FILE_HEADER_SIZE = 1024
 FRAME_HEADER_SIZE = 64
@@ -167,7 +167,7 @@ def _read_gain_map(path):
     return None
 
 
-class FRMS6DataSet(MemoryDataSet):
+class FRMS6DataSet(DecodedFileDataSet):
     """
     Parameters (reference frms6.py:412-440)
     ----------
@@ -187,37 +187,26 @@ class FRMS6DataSet(MemoryDataSet):
     shard : (rank, world), optional
         one process per GPU: decode and hold only this rank's block of the first nav axis
     """
-    CHUNK_BYTES = MIBDataSet.CHUNK_BYTES         # file bytes per copy + decode step (two in flight)
-    COPY_THREADS = MIBDataSet.COPY_THREADS
-    #: as for .mib files: decoded bytes this process may keep in HBM (None: what is free); more is streamed
-    MAX_RESIDENT_BYTES = None
-    STREAM_WINDOW_BYTES = MIBDataSet.STREAM_WINDOW_BYTES
+    KIND = "FRMS6 set"
+    DECODE_KERNEL = "ltmi_frms6_decode"
 
     def __init__(self, path, enable_offset_correction=True, gain_map_path=None, dest_dtype=None,
                  nav_shape=None, sig_shape=None, sync_offset=0, io_backend=None, num_partitions=None,
                  shard=None):
-        if io_backend is not None:
-            raise ValueError("alternative I/O backends are not part of this build")
+        DecodedFileDataSet.__init__(self, path, num_partitions, shard, io_backend)
         if dest_dtype is not None:
             warnings.warn("dest_dtype is now handled per `get_tiles` call, and ignored here",
                           DeprecationWarning)
-        self._path = str(path)
         self._enable_offset_correction = bool(enable_offset_correction)
         self._gain_map_path = None if gain_map_path is None else str(gain_map_path)
         self._nav_arg = tuple(nav_shape) if nav_shape else None
         self._sig_arg = tuple(sig_shape) if sig_shape else None
         self._sync_offset_arg = int(sync_offset)
-        self._num_partitions_arg = num_partitions
-        self._shard_arg = shard
         self._scan = None
         self._hdr_info = None
         self._headers = None
         self._dark_frame = None
         self._gain_map = None
-        self._image_count = None
-        self.decode_seconds = None
-        self.decode_bytes = None
-        self._streamed = None
 
     # --- host side: which files, which frames -------------------------------------------------------
     def _scan_files(self):
@@ -262,62 +251,19 @@ class FRMS6DataSet(MemoryDataSet):
                     counts=counts, starts=np.cumsum([0] + counts))
 
     def initialize(self, executor):
-        device = getattr(executor, 'gpu_id', None)
-        if device is None:
-            raise DataSetException(
-                "FRMS6DataSet decodes the files on the GPU (ltmi_frms6_decode): the executor drives none")
+        device = self._gpu_of(executor)
         self._scan = scan = self._scan_files()
         self._hdr_info, self._headers = scan['hdr'], scan['headers']
         native = scan['native_sig_shape']
         nav_shape = tuple(scan['nav_shape'])
         sig_shape = scan['sig_shape']
-        n_nav = int(prod(nav_shape))
         self._image_count = scan['image_count']
         so = scan['sync_offset']
-        # this process's block of scan positions [p0, p1)
-        local_nav = nav_shape
-        p0, p1 = 0, n_nav
-        if self._shard_arg is not None:
-            rank, world = int(self._shard_arg[0]), int(self._shard_arg[1])
-            if nav_shape[0] % world:
-                raise DataSetException(f"first nav axis {nav_shape[0]} does not split over {world} ranks")
-            local_nav = (nav_shape[0] // world,) + tuple(nav_shape[1:])
-            p0 = rank * int(prod(local_nav))
-            p1 = p0 + int(prod(local_nav))
-        self._streamed = None
-        n_local = p1 - p0
         storage = np.dtype('uint16')
-        frame_bytes = int(prod(native)) * storage.itemsize
-        need = n_local * frame_bytes
-        stride = FRAME_HEADER_SIZE + scan['height'] * scan['width'] * 2
-        if not self._fits_in_hbm(device, executor, need, stride, n_local):
-            # a scan larger than the HBM it may take: windows of it, decoded per partition
-            import torch
-            free_bytes, _ = torch.cuda.mem_get_info(device)
-            window = int(min(self.STREAM_WINDOW_BYTES, max(frame_bytes, free_bytes // 4)))
-            if self.MAX_RESIDENT_BYTES is not None:
-                window = int(min(window, max(frame_bytes, self.MAX_RESIDENT_BYTES)))
-            want = -(-need // window)
-            n_parts = max(int(self._num_partitions_arg or 1), int(want))
-            self._streamed = dict(device=device, executor=executor, p0=p0, sync_offset=so, key=None,
-                                  frames=None)
-            self.decode_seconds, self.decode_bytes = 0.0, 0
-            placeholder = torch.empty(1, dtype=torch.uint8, device=f'cuda:{device}')
-            frames = HipArray(placeholder, (n_local,) + native, storage)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=min(n_parts, max(1, n_local)), shard=self._shard_arg)
-        else:
-            frames = self._decode_to_device(device, executor, p0, p1, so)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=self._num_partitions_arg, shard=self._shard_arg)
-        self._sync_offset = so
-        # scan positions that hold a frame of the files (frame g sits at g - so): the rest are zero frames
-        n_frames = int(scan['starts'][-1])
-        lo = min(n_nav, max(0, -so))
-        hi = max(lo, min(n_nav, n_frames - so))
-        self._valid_frames = None if (lo, hi) == (0, n_nav) else (lo, hi)
+        self._load_frames(executor, device, FrameLayout(
+            nav_shape=nav_shape, sig_shape=sig_shape, native_shape=native, storage=storage,
+            stride=FRAME_HEADER_SIZE + scan['height'] * scan['width'] * 2, n_frames=int(scan['starts'][-1]),
+            sync_offset=so))
         self._dark_frame = None
         if self._enable_offset_correction:
             self._dark_frame = self._get_dark_frame(device, executor).reshape(tuple(sig_shape))
@@ -336,95 +282,32 @@ class FRMS6DataSet(MemoryDataSet):
             image_count=self._image_count)
         return MemoryDataSet.initialize(self, executor)
 
-    def _upload_and_decode(self, device, headers, starts, g0, g1, consume):
-        """Frames [g0, g1) of the files `headers` (frame numbers run on across them, `starts`: first frame of
-        each) -> device, in chunks of whole frame records of ONE file, two in flight: file bytes through the
-        pinned bounce buffers, `ltmi_frms6_decode` behind each copy on the copy stream, then
-        `consume(c0, c1, decode, copy_stream)` with `decode(dst_ptr)` enqueueing the decode of the chunk's frames
-        [c0, c1)."""
-        import torch
+    def _frame_source(self, device, headers=None, starts=None):
+        """the signal files; or the files `headers`, frame numbers running on across them (`starts`: first frame
+        of each)"""
         from libertem_amd import hip
-        from concurrent.futures import ThreadPoolExecutor
         scan = self._scan
+        if headers is None:
+            headers, starts = scan['headers'][1:], scan['starts']
         h, w, binning = scan['height'], scan['width'], scan['binning']
         stride = FRAME_HEADER_SIZE + h * w * 2
-        chunk = int(max(1, min(g1 - g0, self.CHUNK_BYTES // stride)))
-        pinned = _bounce_buffers(torch, chunk * stride)
-        raw = [torch.empty(chunk * stride, dtype=torch.uint8, device=f'cuda:{device}') for _ in range(2)]
-        free = [None, None]
-        copy_stream = torch.cuda.Stream(device=device)
-        copy_stream.wait_stream(torch.cuda.current_stream(device))     # (the zero fill)
-        pool = ThreadPoolExecutor(self.COPY_THREADS)
-        i, g = 0, g0
-        fi = int(np.searchsorted(starts, g0, side='right') - 1)
-        mapping = None
-        while g < g1:
-            if g >= int(starts[fi + 1]):
-                fi, mapping = fi + 1, None
-                continue
-            if mapping is None:
-                mapping = np.memmap(headers[fi]['path'], dtype=np.uint8, mode='r')     # one mapping at a time
+        mapped = {}
+
+        def fill(pool, host, g, n):
+            # whole frame records of ONE file: a chunk never spans two files
+            fi = int(np.searchsorted(starts, g, side='right') - 1)
+            if fi not in mapped:
+                mapped.clear()                                              # one mapping at a time
+                mapped[fi] = np.memmap(headers[fi]['path'], dtype=np.uint8, mode='r')
             a = g - int(starts[fi])                                     # first frame of the chunk in its file
-            n = min(chunk, g1 - g, int(starts[fi + 1]) - g)             # a chunk never spans two files
-            slot = i & 1
-            if free[slot] is not None:
-                free[slot].synchronize()
-            nb = n * stride
-            self._host_copy(pool, pinned[slot].numpy(), 0, mapping, FILE_HEADER_SIZE + a * stride, nb)
-            with torch.cuda.stream(copy_stream):
-                raw[slot][:nb].copy_(pinned[slot][:nb], non_blocking=True)
-                src = raw[slot].data_ptr() + FRAME_HEADER_SIZE
+            n = min(n, int(starts[fi + 1]) - g)
+            _host_copy(pool, host, 0, mapped[fi], FILE_HEADER_SIZE + a * stride, n * stride)
+            return n
 
-                def decode(dst_ptr, src=src, n=n):
-                    hip.frms6_decode(device, src, stride, n, h, w, binning, dst_ptr, np.uint16,
-                                     stream=copy_stream.cuda_stream)
-                consume(g, g + n, decode, copy_stream)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-                free[slot] = ev
-            g += n
-            i += 1
-        copy_stream.synchronize()
-        pool.shutdown()
-
-    def _decode_to_device(self, device, executor, p0, p1, sync_offset):
-        """scan positions [p0, p1) -> HipArray (p1 - p0,) + native sig shape, uint16"""
-        import time
-        import torch
-        scan = self._scan
-        sig = scan['native_sig_shape']
-        stride = FRAME_HEADER_SIZE + scan['height'] * scan['width'] * 2
-        storage = np.dtype('uint16')
-        n = p1 - p0
-        n_frames = int(scan['starts'][-1])
-        g0 = max(p0 + sync_offset, 0)
-        g1 = min(p1 + sync_offset, n_frames)
-        n_src = max(0, g1 - g0)
-        if getattr(executor, '_make_current', None) is not None:
-            executor._make_current()
-        need = n * int(prod(sig)) * storage.itemsize
-        free_bytes, _ = torch.cuda.mem_get_info(device)
-        if need + 2 * min(self.CHUNK_BYTES, max(n_src, 1) * stride) > free_bytes:
-            raise DataSetException(
-                f"{n} decoded frames of {sig[0]}x{sig[1]} {storage} need {need / 2**30:.1f} GiB of HBM, "
-                f"{free_bytes / 2**30:.1f} GiB are free on GPU {device}: fewer frames per partition "
-                "(num_partitions), a part of the scan (nav_shape + sync_offset) or a shard per GPU "
-                "(shard=(rank, world))")
-        t0 = time.perf_counter()
-        out = HipArray.empty((n,) + sig, storage, device) if n_src == n else \
-            HipArray.zeros((n,) + sig, storage, device)             # blank frames stay zero
-        if n_src > 0:
-            def consume(c0, c1, decode, copy_stream):
-                decode(out.rows(c0 - sync_offset - p0, c1 - sync_offset - p0).data_ptr())
-            self._upload_and_decode(device, scan['headers'][1:], scan['starts'], g0, g1, consume)
-        torch.cuda.current_stream(device).synchronize()
-        if self._streamed is not None:
-            self.decode_seconds += time.perf_counter() - t0
-            self.decode_bytes += n_src * stride
-        else:
-            self.decode_seconds = time.perf_counter() - t0
-            self.decode_bytes = n_src * stride
-        return out
+        def decode(src_ptr, n, dst_ptr, stream):
+            hip.frms6_decode(device, src_ptr + FRAME_HEADER_SIZE, stride, n, h, w, binning, dst_ptr, np.uint16,
+                             stream=stream)
+        return fill, decode
 
     def _get_dark_frame(self, device, executor):
         """float32 mean of the frames of file 000 (native sig shape): unfolded by `ltmi_frms6_decode`, summed
@@ -440,8 +323,7 @@ class FRMS6DataSet(MemoryDataSet):
             raise DataSetException("%s holds no dark frame: pass enable_offset_correction=False" % header['path'])
         if getattr(executor, '_make_current', None) is not None:
             executor._make_current()
-        stride = FRAME_HEADER_SIZE + scan['height'] * scan['width'] * 2
-        chunk = int(max(1, min(num_frames, self.CHUNK_BYTES // stride)))
+        chunk = int(max(1, min(num_frames, self.CHUNK_BYTES // self._layout.stride)))
         total = HipArray.zeros((n_px,), np.int64, device)
         decoded = [HipArray.empty((chunk,) + sig, np.uint16, device) for _ in range(2)]
         ws_bytes = hip.sum_frames_workspace(chunk, n_px, np.int64)
@@ -455,37 +337,12 @@ class FRMS6DataSet(MemoryDataSet):
             decode(buf.data_ptr())
             hip.sum_frames(device, buf.data_ptr(), np.uint16, c1 - c0, n_px, n_px, total.data_ptr(), np.int64,
                            True, ws.data_ptr(), stream=copy_stream)
-        self._upload_and_decode(device, [header], np.array([0, num_frames]), 0, num_frames, consume)
+        self._upload_and_decode(device, self._frame_source(device, [header], np.array([0, num_frames])), 0,
+                                num_frames, consume)
         torch.cuda.current_stream(device).synchronize()
         return total.cpu().astype(np.float32).reshape(sig) / num_frames
 
-    # the HBM budget, the window of a streamed partition and the threaded host copy are those of .mib files
-    _fits_in_hbm = MIBDataSet._fits_in_hbm
-    device_frames = MIBDataSet.device_frames
-    _host_copy = staticmethod(MIBDataSet._host_copy)
-
-    @property
-    def stable_device_tiles(self):
-        return self._streamed is None
-
-    @property
-    def is_streamed(self):
-        """the decoded frames do not stay in HBM: every partition decodes its own from the files"""
-        return self._streamed is not None
-
-    @property
-    def data(self):
-        if self._streamed is not None:
-            raise DataSetException(
-                "this FRMS6 set is streamed (larger than the HBM it may take): there is no resident "
-                "array of its frames -- run UDFs over it, or load a part (nav_shape + sync_offset)")
-        return MemoryDataSet.data.fget(self)
-
     # --- the reference's descriptive surface --------------------------------------------------------
-    @property
-    def path(self):
-        return self._path
-
     @property
     def dtype(self):
         """float32 with offset correction (what the corrected tiles are), uint16 without (frms6.py:515-516)"""

@@ -6,8 +6,8 @@ synchronised on the host from their block headers alone, like the reference's K2
 pixels are never touched on the host: where the reference decodes every block of every tile with two nested
 numba loops (decode_k2is, k2is.py:104-164), `initialize()` streams the file bytes ONCE through pinned bounce
 buffers into HBM, `ltmi_k2is_decode` (csrc/ltmi_k2is.hip) unpacks them behind each copy, and the dataset is a
-device-resident uint16 array from then on.  An acquisition that does not fit is STREAMED per partition, as for
-.mib files (mib.py).
+device-resident uint16 array from then on.  An acquisition that does not fit is STREAMED per partition
+(decoded.py).
 
 Scan geometry: the time-series mode of the reference (no scan size known from a .gtg file): `nav_shape`
 defaults to (frames with the shutter flag set,), `sync_offset=None` is the files' own offset (whole frames
@@ -23,10 +23,9 @@ import glob
 import numpy as np
 
 from libertem_amd.common.math import prod
-from libertem_amd.common.hiparray import HipArray
 from .base import DataSetException, DataSetMeta
 from .memory import MemoryDataSet
-from .mib import MIBDataSet, _bounce_buffers
+from .decoded import DecodedFileDataSet, FrameLayout, _host_copy
 
 HEADER_SIZE = 40
 BLOCK_SIZE = 0x5758
@@ -190,7 +189,7 @@ def validate_sync(sectors):
                      f"the {name} frame of {s.path} is not whole or not frame {frame_id}")
 
 
-class K2ISDataSet(MemoryDataSet):
+class K2ISDataSet(DecodedFileDataSet):
     """
     Parameters (reference k2is.py:733-755)
     ----------
@@ -207,28 +206,17 @@ class K2ISDataSet(MemoryDataSet):
     shard : (rank, world), optional
         one process per GPU: decode and hold only this rank's block of the first nav axis
     """
-    CHUNK_BYTES = MIBDataSet.CHUNK_BYTES         # file bytes per copy + decode step (two in flight)
-    COPY_THREADS = MIBDataSet.COPY_THREADS
-    #: as for .mib files: decoded bytes this process may keep in HBM (None: what is free); more is streamed
-    MAX_RESIDENT_BYTES = None
-    STREAM_WINDOW_BYTES = MIBDataSet.STREAM_WINDOW_BYTES
+    KIND = "K2IS acquisition"
+    DECODE_KERNEL = "ltmi_k2is_decode"
 
     def __init__(self, path, nav_shape=None, sig_shape=None, sync_offset=None, io_backend=None,
                  num_partitions=None, shard=None):
-        if io_backend is not None:
-            raise ValueError("alternative I/O backends are not part of this build")
-        self._path = str(path)
+        DecodedFileDataSet.__init__(self, path, num_partitions, shard, io_backend)
         self._nav_arg = tuple(nav_shape) if nav_shape else None
         self._sig_arg = tuple(sig_shape) if sig_shape else None
         self._sync_offset_arg = None if sync_offset is None else int(sync_offset)
-        self._num_partitions_arg = num_partitions
-        self._shard_arg = shard
         self._scan = None
         self._sectors = None
-        self._image_count = None
-        self.decode_seconds = None
-        self.decode_bytes = None
-        self._streamed = None
 
     # --- host side: which files, which blocks -------------------------------------------------------
     def _get_files(self):
@@ -268,10 +256,7 @@ class K2ISDataSet(MemoryDataSet):
                     last_offsets=[s.last * BLOCK_SIZE for s in sectors])
 
     def initialize(self, executor):
-        device = getattr(executor, 'gpu_id', None)
-        if device is None:
-            raise DataSetException(
-                "K2ISDataSet decodes the files on the GPU (ltmi_k2is_decode): the executor drives none")
+        device = self._gpu_of(executor)
         self._scan = scan = self._scan_files()
         nav_shape = tuple(scan['nav_shape'])
         sig_shape = self._sig_arg
@@ -279,151 +264,34 @@ class K2ISDataSet(MemoryDataSet):
             sig_shape = SIG_SHAPE
         elif int(prod(sig_shape)) != int(prod(SIG_SHAPE)):
             raise DataSetException("sig_shape must be of size: %s" % int(prod(SIG_SHAPE)))
-        n_nav = int(prod(nav_shape))
         self._image_count = scan['image_count']
         so = scan['sync_offset']
-        # this process's block of scan positions [p0, p1)
-        local_nav = nav_shape
-        p0, p1 = 0, n_nav
-        if self._shard_arg is not None:
-            rank, world = int(self._shard_arg[0]), int(self._shard_arg[1])
-            if nav_shape[0] % world:
-                raise DataSetException(f"first nav axis {nav_shape[0]} does not split over {world} ranks")
-            local_nav = (nav_shape[0] // world,) + tuple(nav_shape[1:])
-            p0 = rank * int(prod(local_nav))
-            p1 = p0 + int(prod(local_nav))
-        self._streamed = None
-        n_local = p1 - p0
         storage = np.dtype('uint16')
-        frame_bytes = int(prod(SIG_SHAPE)) * storage.itemsize
-        need = n_local * frame_bytes
-        stride = NUM_SECTORS * FRAME_BYTES_PER_SECTOR
-        if not self._fits_in_hbm(device, executor, need, stride, n_local):
-            # an acquisition larger than the HBM it may take: windows of it, decoded per partition
-            import torch
-            free_bytes, _ = torch.cuda.mem_get_info(device)
-            window = int(min(self.STREAM_WINDOW_BYTES, max(frame_bytes, free_bytes // 4)))
-            if self.MAX_RESIDENT_BYTES is not None:
-                window = int(min(window, max(frame_bytes, self.MAX_RESIDENT_BYTES)))
-            want = -(-need // window)
-            n_parts = max(int(self._num_partitions_arg or 1), int(want))
-            self._streamed = dict(device=device, executor=executor, p0=p0, sync_offset=so, key=None,
-                                  frames=None)
-            self.decode_seconds, self.decode_bytes = 0.0, 0
-            placeholder = torch.empty(1, dtype=torch.uint8, device=f'cuda:{device}')
-            frames = HipArray(placeholder, (n_local,) + SIG_SHAPE, storage)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=min(n_parts, max(1, n_local)), shard=self._shard_arg)
-        else:
-            frames = self._decode_to_device(device, executor, p0, p1, so)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=self._num_partitions_arg, shard=self._shard_arg)
-        self._sync_offset = so
-        # scan positions that hold a frame of the files (frame g, counted from the first one with the shutter
-        # flag set, sits at g - so): the rest are the zero frames decoded above
-        lo = min(n_nav, max(0, -so))
-        hi = max(lo, min(n_nav, scan['num_frames_w_shutter'] - so))
-        self._valid_frames = None if (lo, hi) == (0, n_nav) else (lo, hi)
+        # (frames are counted from the first one with the shutter flag set)
+        self._load_frames(executor, device, FrameLayout(
+            nav_shape=nav_shape, sig_shape=sig_shape, native_shape=SIG_SHAPE, storage=storage,
+            stride=NUM_SECTORS * FRAME_BYTES_PER_SECTOR, n_frames=scan['num_frames_w_shutter'], sync_offset=so))
         self._meta = DataSetMeta(shape=self._shape, raw_dtype=storage, sync_offset=so,
                                  image_count=self._image_count)
         return MemoryDataSet.initialize(self, executor)
 
-    def _decode_to_device(self, device, executor, p0, p1, sync_offset):
-        """scan positions [p0, p1) -> HipArray (p1 - p0, 1860, 2048) uint16"""
-        import time
-        import torch
+    def _frame_source(self, device):
         from libertem_amd import hip
-        from concurrent.futures import ThreadPoolExecutor
-        h, w = SIG_SHAPE
-        stride = NUM_SECTORS * FRAME_BYTES_PER_SECTOR           # file bytes of a frame, all sectors
-        storage = np.dtype('uint16')
-        n = p1 - p0
-        g0 = max(p0 + sync_offset, 0)
-        g1 = min(p1 + sync_offset, self._scan['num_frames_w_shutter'])
-        n_src = max(0, g1 - g0)
-        if getattr(executor, '_make_current', None) is not None:
-            executor._make_current()
-        need = n * h * w * storage.itemsize
-        free_bytes, _ = torch.cuda.mem_get_info(device)
-        if need + 2 * min(self.CHUNK_BYTES, max(n_src, 1) * stride) > free_bytes:
-            raise DataSetException(
-                f"{n} decoded frames of {h}x{w} {storage} need {need / 2**30:.1f} GiB of HBM, "
-                f"{free_bytes / 2**30:.1f} GiB are free on GPU {device}: fewer frames per partition "
-                "(num_partitions), a part of the scan (nav_shape + sync_offset) or a shard per GPU "
-                "(shard=(rank, world))")
-        t0 = time.perf_counter()
-        out = HipArray.empty((n, h, w), storage, device) if n_src == n else \
-            HipArray.zeros((n, h, w), storage, device)          # blank frames stay zero
-        if n_src > 0:
-            chunk = int(max(1, min(n_src, self.CHUNK_BYTES // stride)))
-            pinned = _bounce_buffers(torch, chunk * stride)
-            raw = [torch.empty(chunk * stride, dtype=torch.uint8, device=f'cuda:{device}')
-                   for _ in range(2)]
-            free = [None, None]
-            copy_stream = torch.cuda.Stream(device=device)
-            copy_stream.wait_stream(torch.cuda.current_stream(device))     # (the zero fill)
-            pool = ThreadPoolExecutor(self.COPY_THREADS)
-            for i, c0 in enumerate(range(g0, g1, chunk)):
-                c1 = min(g1, c0 + chunk)
-                slot = i & 1
-                if free[slot] is not None:
-                    free[slot].synchronize()
-                host = pinned[slot].numpy()
-                # the chunk's 8 byte ranges, sector after sector (each a multiple of 8 bytes long)
-                part = (c1 - c0) * FRAME_BYTES_PER_SECTOR
-                for s in self._sectors:
-                    self._host_copy(pool, host, s.idx * part, s.map,
-                                    s.first * BLOCK_SIZE + c0 * FRAME_BYTES_PER_SECTOR, part)
-                nb = NUM_SECTORS * part
-                with torch.cuda.stream(copy_stream):
-                    raw[slot][:nb].copy_(pinned[slot][:nb], non_blocking=True)
-                    dst = out.rows(c0 - sync_offset - p0, c1 - sync_offset - p0)
-                    base = raw[slot].data_ptr()
-                    hip.k2is_decode(device, [base + k * part for k in range(NUM_SECTORS)], c1 - c0,
-                                    dst.data_ptr(), storage, stream=copy_stream.cuda_stream)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                    free[slot] = ev
-            copy_stream.synchronize()
-            pool.shutdown()
-        torch.cuda.current_stream(device).synchronize()
-        if self._streamed is not None:
-            self.decode_seconds += time.perf_counter() - t0
-            self.decode_bytes += n_src * stride
-        else:
-            self.decode_seconds = time.perf_counter() - t0
-            self.decode_bytes = n_src * stride
-        return out
 
-    # the HBM budget, the window of a streamed partition and the threaded host copy are those of .mib files
-    _fits_in_hbm = MIBDataSet._fits_in_hbm
-    device_frames = MIBDataSet.device_frames
-    _host_copy = staticmethod(MIBDataSet._host_copy)
+        def fill(pool, host, g, n):
+            # the chunk's 8 byte ranges, sector after sector (each a multiple of 8 bytes long)
+            part = n * FRAME_BYTES_PER_SECTOR
+            for s in self._sectors:
+                _host_copy(pool, host, s.idx * part, s.map, s.first * BLOCK_SIZE + g * FRAME_BYTES_PER_SECTOR, part)
+            return n
 
-    @property
-    def stable_device_tiles(self):
-        return self._streamed is None
-
-    @property
-    def is_streamed(self):
-        """the decoded frames do not stay in HBM: every partition decodes its own from the files"""
-        return self._streamed is not None
-
-    @property
-    def data(self):
-        if self._streamed is not None:
-            raise DataSetException(
-                "this K2IS acquisition is streamed (larger than the HBM it may take): there is no resident "
-                "array of its frames -- run UDFs over it, or load a part (nav_shape + sync_offset)")
-        return MemoryDataSet.data.fget(self)
+        def decode(src_ptr, n, dst_ptr, stream):
+            part = n * FRAME_BYTES_PER_SECTOR
+            hip.k2is_decode(device, [src_ptr + k * part for k in range(NUM_SECTORS)], n, dst_ptr, np.uint16,
+                            stream=stream)
+        return fill, decode
 
     # --- the reference's descriptive surface --------------------------------------------------------
-    @property
-    def path(self):
-        return self._path
-
     @property
     def storage_dtype(self):
         return np.dtype('uint16')

@@ -21,9 +21,9 @@ import warnings
 import numpy as np
 
 from libertem_amd.common.math import prod
-from libertem_amd.common.hiparray import HipArray
 from .base import DataSetException, DataSetMeta
 from .memory import MemoryDataSet
+from .decoded import DecodedFileDataSet, FrameLayout, _host_copy
 
 
 def read_hdr_file(path):
@@ -137,19 +137,7 @@ def get_image_count_and_sig_shape(path, disable_glob=False):
     return sum(f['num_images'] for f in fields), first['image_size']
 
 
-_BOUNCE = {}
-
-
-def _bounce_buffers(torch, nbytes):
-    """two page-locked host buffers of at least `nbytes`, kept for the next load (page-locking 256 MiB
-    costs ~16 ms)"""
-    have = _BOUNCE.get('bufs')
-    if have is None or have[0].numel() < nbytes:
-        _BOUNCE['bufs'] = have = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-    return have
-
-
-class MIBDataSet(MemoryDataSet):
+class MIBDataSet(DecodedFileDataSet):
     """
     Parameters (reference mib.py:1024-1052)
     ----------
@@ -167,22 +155,15 @@ class MIBDataSet(MemoryDataSet):
     shard : (rank, world), optional
         one process per GPU: decode and hold only this rank's block of the first nav axis
     """
-    CHUNK_BYTES = 256 << 20          # file bytes per copy + decode step (two in flight)
-    COPY_THREADS = 8
-    #: decoded bytes this process may keep in HBM (None: what is free).  A block of the scan that needs more
-    #: is STREAMED: no frame is decoded at load time, every partition decodes its frames from the files
-    #: into a window of HBM when its tiles are asked for (partitions of at most STREAM_WINDOW_BYTES).
-    MAX_RESIDENT_BYTES = None
-    STREAM_WINDOW_BYTES = 4 << 30
+    KIND = ".mib series"
+    DECODE_KERNEL = "ltmi_mib_decode"
 
     def __init__(self, path, tileshape=None, scan_size=None, disable_glob=False, nav_shape=None,
                  sig_shape=None, sync_offset=0, io_backend=None, num_partitions=None, shard=None):
-        if io_backend is not None:
-            raise ValueError("alternative I/O backends are not part of this build")
+        DecodedFileDataSet.__init__(self, path, num_partitions, shard, io_backend)
         if tileshape is not None:
             warnings.warn("tileshape argument is ignored and will be removed after 0.6.0",
                           FutureWarning)
-        self._path = str(path)
         nav_shape = tuple(nav_shape) if nav_shape else None
         if scan_size is not None:
             warnings.warn("scan_size argument is deprecated. please specify nav_shape instead",
@@ -197,14 +178,8 @@ class MIBDataSet(MemoryDataSet):
         self._sig_arg = tuple(sig_shape) if sig_shape else None
         self._sync_offset_arg = int(sync_offset)
         self._disable_glob = disable_glob
-        self._num_partitions_arg = num_partitions
-        self._shard_arg = shard
         self._fields = None
         self._files_sorted = None
-        self._image_count = None
-        self.decode_seconds = None
-        self.decode_bytes = None
-        self._streamed = None
 
     # --- host side: which files, which frames ------------------------------------------------------
     def _scan_files(self):
@@ -234,10 +209,7 @@ class MIBDataSet(MemoryDataSet):
         return files, first
 
     def initialize(self, executor):
-        device = getattr(executor, 'gpu_id', None)
-        if device is None:
-            raise DataSetException(
-                "MIBDataSet decodes the files on the GPU (ltmi_mib_decode): the executor drives none")
+        device = self._gpu_of(executor)
         files, first = self._scan_files()
         self._files_sorted, self._fields = files, first
         nav_shape = self._nav_arg
@@ -248,7 +220,6 @@ class MIBDataSet(MemoryDataSet):
             sig_shape = first['image_size']
         elif int(prod(sig_shape)) != int(prod(first['image_size'])):
             raise DataSetException("sig_shape must be of size: %s" % int(prod(first['image_size'])))
-        n_nav = int(prod(nav_shape))
         self._image_count = sum(f['num_images'] for _, f in files)
         so = self._sync_offset_arg
         # (reference io/dataset/base/dataset.py:74: the offset lies in (-image_count, image_count); a
@@ -257,200 +228,47 @@ class MIBDataSet(MemoryDataSet):
             raise DataSetException(
                 f"offset should be in ({-self._image_count}, {self._image_count}), which is "
                 "(-image_count, image_count)")
-        # this process's block of scan positions [p0, p1)
-        local_nav = tuple(nav_shape)
-        p0, p1 = 0, n_nav
-        if self._shard_arg is not None:
-            rank, world = int(self._shard_arg[0]), int(self._shard_arg[1])
-            if nav_shape[0] % world:
-                raise DataSetException(f"first nav axis {nav_shape[0]} does not split over {world} ranks")
-            local_nav = (nav_shape[0] // world,) + tuple(nav_shape[1:])
-            p0 = rank * int(prod(local_nav))
-            p1 = p0 + int(prod(local_nav))
-        self._streamed = None
-        n_local = p1 - p0
-        storage = np.dtype(first['storage_dtype'])
-        need = n_local * int(prod(first['image_size'])) * storage.itemsize
-        stride = first['header_size_bytes'] + first['image_size_bytes']
-        if not self._fits_in_hbm(device, executor, need, stride, n_local):
-            # a series larger than the HBM it may take: windows of it, decoded per partition
-            import torch
-            frame_bytes = int(prod(first['image_size'])) * storage.itemsize
-            free_bytes, _ = torch.cuda.mem_get_info(device)
-            window = int(min(self.STREAM_WINDOW_BYTES, max(frame_bytes, free_bytes // 4)))
-            if self.MAX_RESIDENT_BYTES is not None:
-                window = int(min(window, max(frame_bytes, self.MAX_RESIDENT_BYTES)))
-            want = -(-need // window)
-            n_parts = max(int(self._num_partitions_arg or 1), int(want))
-            self._streamed = dict(device=device, executor=executor, p0=p0, sync_offset=so, key=None,
-                                  frames=None)
-            self.decode_seconds, self.decode_bytes = 0.0, 0
-            placeholder = torch.empty(1, dtype=torch.uint8, device=f'cuda:{device}')
-            frames = HipArray(placeholder, (n_local,) + tuple(first['image_size']), storage)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=min(n_parts, max(1, n_local)), shard=self._shard_arg)
-        else:
-            frames = self._decode_to_device(device, executor, p0, p1, so)
-            MemoryDataSet.__init__(
-                self, data=frames.reshape(local_nav + tuple(sig_shape)), sig_dims=len(sig_shape),
-                num_partitions=self._num_partitions_arg, shard=self._shard_arg)
-        self._sync_offset = so
-        # scan positions that hold a frame of the series (global positions; frame g sits at g - so): the rest are
-        # the zero frames decoded above, which UDFs with `VALID_FRAMES_ONLY` -- and, under a dark frame, all UDFs --
-        # are not handed (udf/base.py `_skips_frameless`)
-        lo = min(n_nav, max(0, -so))
-        hi = max(lo, min(n_nav, self._image_count - so))
-        self._valid_frames = None if (lo, hi) == (0, n_nav) else (lo, hi)
+        self._load_frames(executor, device, FrameLayout(
+            nav_shape=nav_shape, sig_shape=sig_shape, native_shape=first['image_size'],
+            storage=first['storage_dtype'], stride=first['header_size_bytes'] + first['image_size_bytes'],
+            n_frames=self._image_count, sync_offset=so))
         self._meta = DataSetMeta(shape=self._shape, raw_dtype=np.dtype(first['dtype']),
                                  sync_offset=so, image_count=self._image_count)
         return MemoryDataSet.initialize(self, executor)
 
-    def _decode_to_device(self, device, executor, p0, p1, sync_offset):
-        """scan positions [p0, p1) -> HipArray (p1 - p0, H, W) of the storage dtype"""
-        import time
-        import torch
+    def _frame_source(self, device):
         from libertem_amd import hip
         f = self._fields
         h, w = f['image_size']
         stride = f['header_size_bytes'] + f['image_size_bytes']
         quad = f['mib_kind'] == 'r' and f['num_chips'] > 1
         storage = np.dtype(f['storage_dtype'])
-        n = p1 - p0
         # frame g of the series (files in sequence order) sits at scan position g - sync_offset
-        g0 = max(p0 + sync_offset, 0)
-        g1 = min(p1 + sync_offset, self._image_count)
-        n_src = max(0, g1 - g0)
-        if getattr(executor, '_make_current', None) is not None:
-            executor._make_current()
-        need = n * h * w * storage.itemsize
-        free_bytes, _ = torch.cuda.mem_get_info(device)
-        if need + 2 * min(self.CHUNK_BYTES, max(n_src, 1) * stride) > free_bytes:
-            raise DataSetException(
-                f"{n} decoded frames of {h}x{w} {storage} need {need / 2**30:.1f} GiB of HBM, "
-                f"{free_bytes / 2**30:.1f} GiB are free on GPU {device}: fewer frames per partition "
-                "(num_partitions), a part of the scan (nav_shape + sync_offset) or a shard per GPU "
-                "(shard=(rank, world))")
-        t0 = time.perf_counter()
-        out = HipArray.empty((n, h, w), storage, device) if n_src == n else \
-            HipArray.zeros((n, h, w), storage, device)          # blank frames stay zero
-        if n_src > 0:
-            chunk = int(max(1, min(n_src, self.CHUNK_BYTES // stride)))
-            pinned = _bounce_buffers(torch, chunk * stride)
-            raw = [torch.empty(chunk * stride, dtype=torch.uint8, device=f'cuda:{device}')
-                   for _ in range(2)]
-            free = [None, None]
-            copy_stream = torch.cuda.Stream(device=device)
-            copy_stream.wait_stream(torch.cuda.current_stream(device))     # (the zero fill)
-            starts = np.cumsum([0] + [fl['num_images'] for _, fl in self._files_sorted])
-            maps = {}
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(self.COPY_THREADS)
-            for i, c0 in enumerate(range(g0, g1, chunk)):
-                c1 = min(g1, c0 + chunk)
-                slot = i & 1
-                if free[slot] is not None:
-                    free[slot].synchronize()
-                host = pinned[slot].numpy()
-                # file bytes of frames [c0, c1), file by file, packed at the common frame stride
-                fi = int(np.searchsorted(starts, c0, side='right') - 1)
-                g = c0
-                while g < c1:
-                    fn, fl = self._files_sorted[fi]
-                    a = g - int(starts[fi])
-                    b = min(fl['num_images'], a + (c1 - g))
-                    if fi not in maps:
-                        maps.clear()                                       # one mapping at a time
-                        maps[fi] = np.memmap(fn, dtype=np.uint8, mode='r')
-                    self._host_copy(pool, host, (g - c0) * stride, maps[fi], a * stride,
-                                    (b - a) * stride)
-                    g += b - a
-                    fi += 1
-                nb = (c1 - c0) * stride
-                with torch.cuda.stream(copy_stream):
-                    raw[slot][:nb].copy_(pinned[slot][:nb], non_blocking=True)
-                    dst = out.rows(c0 - sync_offset - p0, c1 - sync_offset - p0)
-                    hip.mib_decode(device, raw[slot].data_ptr(), stride, f['header_size_bytes'],
-                                   f['mib_kind'], f['bits_per_pixel'], quad, c1 - c0, h, w,
-                                   dst.data_ptr(), storage, stream=copy_stream.cuda_stream)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-                    free[slot] = ev
-            copy_stream.synchronize()
-            pool.shutdown()
-        torch.cuda.current_stream(device).synchronize()
-        if self._streamed is not None:
-            self.decode_seconds += time.perf_counter() - t0
-            self.decode_bytes += n_src * stride
-        else:
-            self.decode_seconds = time.perf_counter() - t0
-            self.decode_bytes = n_src * stride
-        return out
+        starts = np.cumsum([0] + [fl['num_images'] for _, fl in self._files_sorted])
+        maps = {}
 
-    def _fits_in_hbm(self, device, executor, need, stride, n_local):
-        import torch
-        if getattr(executor, '_make_current', None) is not None:
-            executor._make_current()
-        if self.MAX_RESIDENT_BYTES is not None and need > self.MAX_RESIDENT_BYTES:
-            return False
-        free_bytes, _ = torch.cuda.mem_get_info(device)
-        return need + 2 * min(self.CHUNK_BYTES, max(n_local, 1) * stride) <= free_bytes
+        def fill(pool, host, g, n):
+            # file bytes of frames [g, g + n), file by file, packed at the common frame stride
+            fi = int(np.searchsorted(starts, g, side='right') - 1)
+            done = 0
+            while done < n:
+                fn, fl = self._files_sorted[fi]
+                a = g + done - int(starts[fi])
+                b = min(fl['num_images'], a + (n - done))
+                if fi not in maps:
+                    maps.clear()                                       # one mapping at a time
+                    maps[fi] = np.memmap(fn, dtype=np.uint8, mode='r')
+                _host_copy(pool, host, done * stride, maps[fi], a * stride, (b - a) * stride)
+                done += b - a
+                fi += 1
+            return n
 
-    @property
-    def stable_device_tiles(self):
-        return self._streamed is None
-
-    @property
-    def is_streamed(self):
-        """the decoded frames do not stay in HBM: every partition decodes its own from the files"""
-        return self._streamed is not None
-
-    @property
-    def data(self):
-        if self._streamed is not None:
-            raise DataSetException(
-                "this .mib series is streamed (larger than the HBM it may take): there is no resident "
-                "array of its frames -- run UDFs over it, or load a part (nav_shape + sync_offset)")
-        return MemoryDataSet.data.fget(self)
-
-    def device_frames(self, local0, n):
-        st = self._streamed
-        if st is None:
-            return MemoryDataSet.device_frames(self, local0, n)
-        if st['key'] != (local0, n):
-            st['frames'] = None                     # (one window at a time)
-            st['key'] = None
-            p = st['p0'] + local0
-            st['frames'] = self._decode_to_device(st['device'], st['executor'], p, p + n,
-                                                  st['sync_offset'])
-            st['key'] = (local0, n)
-        return st['frames'], 0
-
-    @staticmethod
-    def _host_copy(pool, dst, dst_off, src, src_off, nbytes, piece=16 << 20):
-        """file mapping -> pinned buffer on several threads (one memcpy stream reads the page cache at
-        ~12 GB/s, a fifth of what the host link takes)"""
-        if nbytes <= piece:
-            dst[dst_off:dst_off + nbytes] = src[src_off:src_off + nbytes]
-            return
-        try:
-            # the library's copy pool: one thread per L3 domain of the host (csrc/ltmi_capi.cpp)
-            from libertem_amd import hip
-            hip.host_copy(dst[dst_off:dst_off + nbytes], np.asarray(src[src_off:src_off + nbytes]))
-            return
-        except Exception:                               # noqa: BLE001  (e.g. a source that is not contiguous)
-            pass
-
-        def run(o):
-            n = min(piece, nbytes - o)
-            dst[dst_off + o:dst_off + o + n] = src[src_off + o:src_off + o + n]
-        list(pool.map(run, range(0, nbytes, piece)))
+        def decode(src_ptr, n, dst_ptr, stream):
+            hip.mib_decode(device, src_ptr, stride, f['header_size_bytes'], f['mib_kind'], f['bits_per_pixel'],
+                           quad, n, h, w, dst_ptr, storage, stream=stream)
+        return fill, decode
 
     # --- the reference's descriptive surface --------------------------------------------------------
-    @property
-    def path(self):
-        return self._path
-
     @property
     def storage_dtype(self):
         """dtype of the decoded pixels in HBM (the declared `dtype` follows the reference)"""

@@ -159,3 +159,21 @@ def test_streamed_like_resident(ctx, filesets, masks, monkeypatch, sync_offset):
         arr, row0 = ds.device_frames(p._local0, p._num_frames)
         assert np.array_equal(arr.rows(row0, row0 + p._num_frames).cpu().reshape((-1,) + SIG),
                               want[p._start_frame:p._start_frame + p._num_frames])
+
+
+def test_four_chunks_in_one_decode(ctx, filesets):
+    """a frame per copy + decode step: four chunks, each bounce buffer used twice, every chunk after the first at
+    an offset into the sector files and into the decoded array"""
+    from libertem_amd.io.dataset.k2is import K2ISDataSet
+    path, frames = filesets['plain']
+    assert len(frames) == 4
+    want_bytes = ctx.load('k2is', path=path).decode_bytes
+    old = K2ISDataSet.CHUNK_BYTES
+    K2ISDataSet.CHUNK_BYTES = 8 * 32 * synth.BLOCK_SIZE
+    try:
+        ds = ctx.load('k2is', path=path)
+    finally:
+        K2ISDataSet.CHUNK_BYTES = old
+    assert not ds.is_streamed
+    assert np.array_equal(ds.data.cpu().reshape(frames.shape), frames)
+    assert ds.decode_bytes == want_bytes == 4 * 8 * 32 * synth.BLOCK_SIZE
