@@ -352,6 +352,30 @@ int ltmi_apply_masks_csr(ltmi_masks *m, const int64_t *indptr, const int32_t *in
                          int data_dtype, const int32_t *rows, int64_t row0, int64_t n_frames, void *out,
                          int64_t ld_out, int accumulate, void *stream, int *handled);
 int ltmi_csr_max_masks(void);
+/* The two sums that are functions of the stored entries alone, on the triple in place (no dense frames).  Both
+ * rely on canonical rows, both skip a stored index outside [0, n_px) instead of following it, both are exact for
+ * integer data and bitwise repeatable.  out_dtype: LTMI_F32 or LTMI_F64.  n_frames == 0 launches nothing.
+ *
+ * ltmi_csr_sum_sig: out[i] (+)= sum of the stored entries of frame i -- SumSigUDF on a sparse tile
+ * (src/libertem/udf/sumsigudf.py:30-39 on a scipy.sparse tile).  out: DEVICE (n_frames,).  data dtypes uint8, uint16,
+ * int16, uint32, int32 (summed in int64, converted once: the exact sum, correctly rounded) and float32 (summed in
+ * float64, rounded once; a stored NaN makes its frame NaN).  A frame without entries gives 0. */
+int ltmi_csr_sum_sig(int device, const int64_t *indptr, const int32_t *indices, const void *data, int data_dtype,
+                     const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px, void *out, int out_dtype,
+                     int accumulate, void *stream);
+/* ltmi_csr_sum_frames: out[p] (+)= sum over the n_frames frames of their entry at pixel p -- SumUDF on a sparse
+ * tile (src/libertem/udf/sum.py:43-48).  out: DEVICE (n_px,).  INTEGER data only (uint8, uint16, int16, uint32,
+ * int32; float32 is LTMI_E_DTYPE: a float sum depends on its order, and the dense route's order is the one that is
+ * pinned): every pixel is summed in int64 and converted once.  workspace: DEVICE, ltmi_csr_sum_frames_workspace(n_px)
+ * bytes, 8-byte aligned, the caller's; its contents on entry do not matter and it can serve the next call. */
+int64_t ltmi_csr_sum_frames_workspace(int64_t n_px);
+int ltmi_csr_sum_frames(int device, const int64_t *indptr, const int32_t *indices, const void *data, int data_dtype,
+                        const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px, void *out, int out_dtype,
+                        int accumulate, void *workspace, void *stream);
+/* Which kernel the calling thread's last ltmi_csr_sum_sig / ltmi_csr_sum_frames launched, e.g.
+ * "k_csr_sum_sig<u16,f32>", "k_csr_sum_frames<i32,f64> rows" (" rows": a row list was passed); "" before the first.
+ * A call that fails its argument checks or has n_frames == 0 launches nothing and leaves the string as it was. */
+const char *ltmi_csr_last_kernel(void);
 
 /* ---- detector corrections -------------------------------------------------------------------
  * Replaces CorrectionSet.apply -> detector.correct on a tile (src/libertem/io/corrections/

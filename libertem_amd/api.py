@@ -19,7 +19,7 @@ from libertem_amd.io.dataset import load as _load_dataset
 from libertem_amd.udf.base import UDFRunner
 from libertem_amd.analysis import (
     MasksAnalysis, COMAnalysis, RadialFourierAnalysis, SumAnalysis, DiskMaskAnalysis,
-    RingMaskAnalysis, PointMaskAnalysis,
+    RingMaskAnalysis, PointMaskAnalysis, SumSigAnalysis,
 )
 
 
@@ -157,6 +157,10 @@ class Context:
 
     def create_sum_analysis(self, dataset):
         return SumAnalysis(dataset=dataset, parameters={})
+
+    def create_sumsig_analysis(self, dataset):
+        """per-frame sum over the signal axes (reference api.py create_sumsig_analysis)"""
+        return SumSigAnalysis(dataset=dataset, parameters={})
 
     # --- running -------------------------------------------------------------------------------
     def run(self, job, roi=None, progress=False, corrections=None):

@@ -332,7 +332,8 @@ class HostMappedArray(HipArray):
 class HipCSRArray(HipArray):
     """
     Frames of a CSR triple that is resident in HBM -- logical shape (n, *sig), NO dense copy: what a tile of
-    a raw_csr dataset looks like to the kernels that read sparse frames in place (`ltmi_apply_masks_csr`).
+    a raw_csr dataset looks like to the kernels that read sparse frames in place (`ltmi_apply_masks_csr`,
+    `ltmi_csr_sum_sig`, `ltmi_csr_sum_frames`).
     Everything else calls `materialize()`: the frames densified by `ltmi_csr_densify`.
     `indptr` (int64, starting at 0), `indices` (int32), `values` (storage dtype of `dtype`): device tensors
     of the whole triple, rows canonical; the view covers rows [row0, row0 + n), or the rows `rows32` names

@@ -3,6 +3,8 @@
 //   ltmi_csr_check        one pass over every row: index range, row order, indptr
 //   ltmi_csr_densify      frames of the triple -> a dense tile (zero fill + scatter)
 //   ltmi_apply_masks_csr  out[f, m] (+)= sum_k data[k] * W[indices[k], m] over the stored entries of frame f
+//   ltmi_csr_sum_sig      out[f] (+)= sum_k data[k] over the stored entries of frame f
+//   ltmi_csr_sum_frames   out[p] (+)= sum over the frames of their entry at pixel p
 //
 // The rows are canonical (strictly ascending indices, checked once by ltmi_csr_check): every pixel of a
 // frame is stored at most once, so the scatter uses plain stores and the product needs no atomics.
@@ -160,6 +162,157 @@ static int launch_apply_csr(ltmi_masks *m, const int64_t *indptr, const int32_t 
     return LTMI_OK;
 }
 
+// ---- sums on the stored entries -------------------------------------------------------------------------
+// the kernel of the last sum launched by this thread ("" before the first): ltmi_csr_last_kernel
+thread_local char t_last_kernel[64] = {0};
+
+template <typename T> struct SumAcc { typedef int64_t type; };      // integers: exact
+template <> struct SumAcc<float> { typedef double type; };          // float32: rounded once, at the end
+
+// One wave per frame, lanes striding the row; the 64 partial sums are added in a fixed order (xor shuffles),
+// lane 0 stores.  An index outside [0, n_px) is skipped.
+template <typename T, typename O>
+__global__ void __launch_bounds__(256)
+k_csr_sum_sig(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const T *__restrict__ data,
+              const int32_t *__restrict__ rows, int64_t row0, int64_t n_frames, int64_t n_px, O *__restrict__ out,
+              int accumulate) {
+    typedef typename SumAcc<T>::type A;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t f = wave; f < n_frames; f += n_waves) {
+        const int64_t r = rows ? (int64_t)rows[f] : row0 + f;
+        const int64_t a = indptr[r], b = indptr[r + 1];
+        A acc = A(0);
+        for (int64_t k = a + lane; k < b; k += 64)
+            if ((uint32_t)indices[k] < (uint64_t)n_px) acc += (A)data[k];
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane == 0) out[f] = accumulate ? out[f] + (O)acc : (O)acc;
+    }
+}
+
+// Workgroup (bx, by) owns the CSR_SUM_PX pixels from bx * CSR_SUM_PX -- int64 sums in LDS -- and the frames of
+// split by.  A wave takes 64 frames at a time: lane l finds the sub-range of frame l that falls into the
+// block (binary search in the ascending row), then the wave's four groups of 16 lanes walk one sub-range
+// each and add into LDS (integer adds: any order gives the same bits).  The block's sums go to
+// part[by][pixel] with plain stores; k_csr_sum_frames_store adds the splits.
+constexpr int CSR_SUM_PX = 4096;          // 32 KiB of LDS: four workgroups per CU
+constexpr int CSR_SUM_MIN_FRAMES = 64;    // frames a split holds at least: one trip of one wave
+constexpr int CSR_SUM_MAX_SPLITS = 64;
+constexpr int CSR_SUM_WGS = 1024;         // workgroups wanted at most: four per CU
+
+__device__ __forceinline__ int64_t csr_lower_bound(const int32_t *__restrict__ indices, int64_t a, int64_t b,
+                                                   int64_t p) {
+    while (a < b) {
+        const int64_t m = a + ((b - a) >> 1);
+        if ((int64_t)indices[m] < p) a = m + 1; else b = m;
+    }
+    return a;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_csr_sum_frames(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices, const T *__restrict__ data,
+                 const int32_t *__restrict__ rows, int64_t row0, int64_t n_frames, int64_t n_px,
+                 int64_t frames_per_split, int64_t *__restrict__ part) {
+    __shared__ unsigned long long acc[CSR_SUM_PX];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, n_wv = blockDim.x >> 6;
+    const int grp = lane >> 4, sub = lane & 15;
+    const int64_t p0 = (int64_t)blockIdx.x * CSR_SUM_PX, p1 = min(p0 + (int64_t)CSR_SUM_PX, n_px);
+    const int64_t f0 = (int64_t)blockIdx.y * frames_per_split, f1 = min(f0 + frames_per_split, n_frames);
+    for (int i = threadIdx.x; i < CSR_SUM_PX; i += blockDim.x) acc[i] = 0ull;
+    __syncthreads();
+    for (int64_t base = f0 + (int64_t)wv * 64; base < f1; base += (int64_t)n_wv * 64) {
+        int64_t lo = 0, hi = 0;
+        if (base + lane < f1) {
+            const int64_t f = base + lane;
+            const int64_t r = rows ? (int64_t)rows[f] : row0 + f;
+            const int64_t a = indptr[r], b = indptr[r + 1];
+            // (the first and the last block take the row's own ends: an index below 0 or from n_px on is left to
+            // the range test below)
+            lo = p0 == 0 ? a : csr_lower_bound(indices, a, b, p0);
+            hi = p1 == n_px ? b : csr_lower_bound(indices, lo, b, p1);
+        }
+        const int nf = (int)min((int64_t)64, f1 - base);
+        for (int j0 = 0; j0 < nf; j0 += 4) {
+            const int j = min(j0 + grp, 63);
+            // (both shuffles with every lane active: lane j may belong to a group that has no frame in this trip)
+            const int64_t l = __shfl(lo, j, 64), hj = __shfl(hi, j, 64);
+            const int64_t h = j0 + grp < nf ? hj : l;
+            for (int64_t k = l + sub; k < h; k += 16) {
+                const int64_t i = (int64_t)indices[k] - p0;
+                if ((uint64_t)i < (uint64_t)(p1 - p0)) atomicAdd(&acc[i], (unsigned long long)(int64_t)data[k]);
+            }
+        }
+    }
+    __syncthreads();
+    int64_t *dst = part + (int64_t)blockIdx.y * n_px + p0;
+    for (int64_t i = threadIdx.x; i < p1 - p0; i += blockDim.x) dst[i] = (int64_t)acc[i];
+}
+
+template <typename O>
+__global__ void k_csr_sum_frames_store(const int64_t *__restrict__ part, int n_splits, int64_t n_px,
+                                       O *__restrict__ out, int accumulate) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_px;
+         p += (int64_t)gridDim.x * blockDim.x) {
+        int64_t s = 0;
+        for (int k = 0; k < n_splits; ++k) s += part[(int64_t)k * n_px + p];
+        out[p] = accumulate ? out[p] + (O)s : (O)s;
+    }
+}
+
+static int64_t csr_sum_blocks(int64_t n_px) { return (n_px + CSR_SUM_PX - 1) / CSR_SUM_PX; }
+
+static int csr_sum_max_splits(int64_t n_px) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(CSR_SUM_MAX_SPLITS, CSR_SUM_WGS / csr_sum_blocks(n_px)));
+}
+
+static void csr_sum_name(const char *kernel, const char *tname, int out_dtype, bool rows) {
+    snprintf(t_last_kernel, sizeof(t_last_kernel), "%s<%s,%s>%s", kernel, tname,
+             out_dtype == LTMI_F64 ? "f64" : "f32", rows ? " rows" : "");
+}
+
+template <typename T>
+static int launch_csr_sum_sig(const int64_t *indptr, const int32_t *indices, const void *data, const int32_t *rows,
+                              int64_t row0, int64_t n_frames, int64_t n_px, void *out, int out_dtype, int accumulate,
+                              hipStream_t stream, const char *tname) {
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_frames + 3) / 4, 1 << 20);
+    if (out_dtype == LTMI_F64)
+        hipLaunchKernelGGL((k_csr_sum_sig<T, double>), dim3(blocks), dim3(256), 0, stream, indptr, indices,
+                           (const T *)data, rows, row0, n_frames, n_px, (double *)out, accumulate);
+    else
+        hipLaunchKernelGGL((k_csr_sum_sig<T, float>), dim3(blocks), dim3(256), 0, stream, indptr, indices,
+                           (const T *)data, rows, row0, n_frames, n_px, (float *)out, accumulate);
+    LTMI_HIP(hipGetLastError());
+    csr_sum_name("k_csr_sum_sig", tname, out_dtype, rows != nullptr);
+    return LTMI_OK;
+}
+
+template <typename T>
+static int launch_csr_sum_frames(const int64_t *indptr, const int32_t *indices, const void *data,
+                                 const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px, void *out,
+                                 int out_dtype, int accumulate, int64_t *part, hipStream_t stream,
+                                 const char *tname) {
+    const int64_t n_blocks = csr_sum_blocks(n_px);
+    int64_t splits = std::min<int64_t>(csr_sum_max_splits(n_px),
+                                       (n_frames + CSR_SUM_MIN_FRAMES - 1) / CSR_SUM_MIN_FRAMES);
+    const int64_t per_split = (n_frames + splits - 1) / splits;
+    splits = (n_frames + per_split - 1) / per_split;              // (no split without frames)
+    hipLaunchKernelGGL((k_csr_sum_frames<T>), dim3((unsigned)n_blocks, (unsigned)splits), dim3(256), 0, stream,
+                       indptr, indices, (const T *)data, rows, row0, n_frames, n_px, per_split, part);
+    LTMI_HIP(hipGetLastError());
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_px + 255) / 256, 65535);
+    if (out_dtype == LTMI_F64)
+        hipLaunchKernelGGL((k_csr_sum_frames_store<double>), dim3(blocks), dim3(256), 0, stream, part, (int)splits,
+                           n_px, (double *)out, accumulate);
+    else
+        hipLaunchKernelGGL((k_csr_sum_frames_store<float>), dim3(blocks), dim3(256), 0, stream, part, (int)splits,
+                           n_px, (float *)out, accumulate);
+    LTMI_HIP(hipGetLastError());
+    csr_sum_name("k_csr_sum_frames", tname, out_dtype, rows != nullptr);
+    return LTMI_OK;
+}
+
 void csrframes_destroy(ltmi_masks *m) {
     if (m->img_px) (void)hipFree(m->img_px);
     m->img_px = nullptr;
@@ -248,3 +401,71 @@ extern "C" int ltmi_apply_masks_csr(ltmi_masks *m, const int64_t *indptr, const 
 }
 
 extern "C" int ltmi_csr_max_masks(void) { return ltmi::CSR_MAX_MASKS; }
+
+extern "C" int ltmi_csr_sum_sig(int device, const int64_t *indptr, const int32_t *indices, const void *data,
+                                int data_dtype, const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px,
+                                void *out, int out_dtype, int accumulate, void *stream_) {
+    if (!indptr || !out || n_frames < 0 || n_px <= 0 || row0 < 0)
+        LTMI_FAIL(LTMI_E_INVALID, "ltmi_csr_sum_sig: bad arguments (n_frames=%lld n_px=%lld)", (long long)n_frames,
+                  (long long)n_px);
+    if (out_dtype != LTMI_F32 && out_dtype != LTMI_F64)
+        LTMI_FAIL(LTMI_E_DTYPE, "ltmi_csr_sum_sig: output dtype %s is not supported", ltmi::dtype_name(out_dtype));
+    switch (data_dtype) {
+        case LTMI_U8: case LTMI_U16: case LTMI_I16: case LTMI_U32: case LTMI_I32: case LTMI_F32: break;
+        default:
+            LTMI_FAIL(LTMI_E_DTYPE, "ltmi_csr_sum_sig: data dtype %s is not supported", ltmi::dtype_name(data_dtype));
+    }
+    if (n_frames == 0) return LTMI_OK;
+    LTMI_HIP(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_;
+#define LTMI_CSR_SUM_SIG(T, NAME)                                                                                  \
+    return ltmi::launch_csr_sum_sig<T>(indptr, indices, data, rows, row0, n_frames, n_px, out, out_dtype, accumulate, \
+                                       stream, NAME)
+    switch (data_dtype) {
+        case LTMI_U8: LTMI_CSR_SUM_SIG(uint8_t, "u8");
+        case LTMI_U16: LTMI_CSR_SUM_SIG(uint16_t, "u16");
+        case LTMI_I16: LTMI_CSR_SUM_SIG(int16_t, "i16");
+        case LTMI_U32: LTMI_CSR_SUM_SIG(uint32_t, "u32");
+        case LTMI_I32: LTMI_CSR_SUM_SIG(int32_t, "i32");
+        default: LTMI_CSR_SUM_SIG(float, "f32");
+    }
+#undef LTMI_CSR_SUM_SIG
+}
+
+extern "C" int64_t ltmi_csr_sum_frames_workspace(int64_t n_px) {
+    if (n_px <= 0) return 0;
+    return (int64_t)ltmi::csr_sum_max_splits(n_px) * n_px * (int64_t)sizeof(int64_t);
+}
+
+extern "C" int ltmi_csr_sum_frames(int device, const int64_t *indptr, const int32_t *indices, const void *data,
+                                   int data_dtype, const int32_t *rows, int64_t row0, int64_t n_frames, int64_t n_px,
+                                   void *out, int out_dtype, int accumulate, void *workspace, void *stream_) {
+    if (!indptr || !out || !workspace || n_frames < 0 || n_px <= 0 || row0 < 0)
+        LTMI_FAIL(LTMI_E_INVALID, "ltmi_csr_sum_frames: bad arguments (n_frames=%lld n_px=%lld)",
+                  (long long)n_frames, (long long)n_px);
+    if (out_dtype != LTMI_F32 && out_dtype != LTMI_F64)
+        LTMI_FAIL(LTMI_E_DTYPE, "ltmi_csr_sum_frames: output dtype %s is not supported",
+                  ltmi::dtype_name(out_dtype));
+    switch (data_dtype) {
+        case LTMI_U8: case LTMI_U16: case LTMI_I16: case LTMI_U32: case LTMI_I32: break;
+        default:
+            LTMI_FAIL(LTMI_E_DTYPE, "ltmi_csr_sum_frames: data dtype %s is not supported (integer data only)",
+                      ltmi::dtype_name(data_dtype));
+    }
+    if (n_frames == 0) return LTMI_OK;
+    LTMI_HIP(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_;
+#define LTMI_CSR_SUM_FRAMES(T, NAME)                                                                          \
+    return ltmi::launch_csr_sum_frames<T>(indptr, indices, data, rows, row0, n_frames, n_px, out, out_dtype, \
+                                          accumulate, (int64_t *)workspace, stream, NAME)
+    switch (data_dtype) {
+        case LTMI_U8: LTMI_CSR_SUM_FRAMES(uint8_t, "u8");
+        case LTMI_U16: LTMI_CSR_SUM_FRAMES(uint16_t, "u16");
+        case LTMI_I16: LTMI_CSR_SUM_FRAMES(int16_t, "i16");
+        case LTMI_U32: LTMI_CSR_SUM_FRAMES(uint32_t, "u32");
+        default: LTMI_CSR_SUM_FRAMES(int32_t, "i32");
+    }
+#undef LTMI_CSR_SUM_FRAMES
+}
+
+extern "C" const char *ltmi_csr_last_kernel(void) { return ltmi::t_last_kernel; }

@@ -37,6 +37,7 @@ EXPORTS = (
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
+    'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
     'ltmi_masks_last_kernel', 'ltmi_comm_unique_id', 'ltmi_comm_create', 'ltmi_comm_destroy',
     'ltmi_comm_all_gather', 'ltmi_comm_all_reduce_sum', 'ltmi_comm_library_info',
@@ -288,6 +289,12 @@ def lib():
         L.ltmi_csr_densify.argtypes = [i32, vp, vp, vp, i32, vp, i64, i64, i64, vp, i64, vp]
         L.ltmi_apply_masks_csr.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, i32, vp, c.POINTER(i32)]
         L.ltmi_csr_max_masks.argtypes = []
+        L.ltmi_csr_sum_sig.argtypes = [i32, vp, vp, vp, i32, vp, i64, i64, i64, vp, i32, i32, vp]
+        L.ltmi_csr_sum_frames_workspace.argtypes = [i64]
+        L.ltmi_csr_sum_frames_workspace.restype = i64
+        L.ltmi_csr_sum_frames.argtypes = [i32, vp, vp, vp, i32, vp, i64, i64, i64, vp, i32, i32, vp, vp]
+        L.ltmi_csr_last_kernel.argtypes = []
+        L.ltmi_csr_last_kernel.restype = c.c_char_p
         L.ltmi_masks_set_tuning.argtypes = [vp, i32, i32, i32]
         L.ltmi_masks_last_kernel.argtypes = [vp]
         L.ltmi_comm_unique_id.argtypes = [vp]
@@ -612,6 +619,40 @@ def csr_densify(device, indptr_ptr, indices_ptr, data_ptr, data_dtype, rows_ptr,
         ctypes.c_void_p(data_ptr or None), dtype_code(data_dtype), ctypes.c_void_p(rows_ptr or None), int(row0),
         int(n_frames), int(n_px), ctypes.c_void_p(out_ptr), int(ld_out),
         stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_csr_densify')
+
+
+def csr_sum_sig(device, indptr_ptr, indices_ptr, data_ptr, data_dtype, rows_ptr, row0, n_frames, n_px, out_ptr,
+                out_dtype, accumulate, stream=None):
+    """out[i] (+)= sum of the stored entries of the sparse frame row0 + i (or rows[i]: device int32) of a CSR
+    triple in HBM; out: float32 / float64 (n_frames,)"""
+    check(lib().ltmi_csr_sum_sig(
+        int(device), ctypes.c_void_p(indptr_ptr), ctypes.c_void_p(indices_ptr or None),
+        ctypes.c_void_p(data_ptr or None), dtype_code(data_dtype), ctypes.c_void_p(rows_ptr or None), int(row0),
+        int(n_frames), int(n_px), ctypes.c_void_p(out_ptr), dtype_code(out_dtype), 1 if accumulate else 0,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_csr_sum_sig')
+
+
+def csr_sum_frames_workspace(n_px):
+    """bytes of scratch ltmi_csr_sum_frames needs for frames of n_px pixels"""
+    return int(lib().ltmi_csr_sum_frames_workspace(int(n_px)))
+
+
+def csr_sum_frames(device, indptr_ptr, indices_ptr, data_ptr, data_dtype, rows_ptr, row0, n_frames, n_px, out_ptr,
+                   out_dtype, accumulate, workspace_ptr, stream=None):
+    """out[p] (+)= sum over the sparse frames row0 + i (or rows[i]: device int32), 0 <= i < n_frames, of their
+    entry at pixel p; integer data, out: float32 / float64 (n_px,)"""
+    check(lib().ltmi_csr_sum_frames(
+        int(device), ctypes.c_void_p(indptr_ptr), ctypes.c_void_p(indices_ptr or None),
+        ctypes.c_void_p(data_ptr or None), dtype_code(data_dtype), ctypes.c_void_p(rows_ptr or None), int(row0),
+        int(n_frames), int(n_px), ctypes.c_void_p(out_ptr), dtype_code(out_dtype), 1 if accumulate else 0,
+        ctypes.c_void_p(workspace_ptr), stream if isinstance(stream, int) else _stream_ptr(stream)),
+        'ltmi_csr_sum_frames')
+
+
+def csr_last_kernel():
+    """the kernel the calling thread's last csr_sum_sig / csr_sum_frames launched, e.g. 'k_csr_sum_sig<u16,f32> rows'
+    ('' before the first)"""
+    return lib().ltmi_csr_last_kernel().decode()
 
 
 def sum_frames_workspace(n_frames, n_px, out_dtype):

@@ -6,8 +6,9 @@ detectors write it.  Same parameters, sidecar layout and errors as the reference
 frames live: the reference maps the three files and hands scipy.sparse tiles to the UDFs
 (raw_csr.py:481-648); here `initialize()` uploads this process's part of the triple ONCE, checks it on the
 device (`ltmi_csr_check`) and keeps it in HBM.  Tiles are `HipCSRArray` views of it: `ApplyMasksUDF` multiplies
-the stored entries in place (`ltmi_apply_masks_csr`), every other UDF is handed the frames densified into
-one window of HBM that the tiles of a partition share (`ltmi_csr_densify`).
+the stored entries in place (`ltmi_apply_masks_csr`), `SumSigUDF` and `SumUDF` sum them in place
+(`ltmi_csr_sum_sig`, `ltmi_csr_sum_frames`), every other UDF is handed the frames densified into one window of HBM
+that the tiles of a partition share (`ltmi_csr_densify`).
 
 On a CPU executor the tiles are slices of the memory-mapped triple, densified on the host: a convenience
 for NumPy UDFs, not a hot path.

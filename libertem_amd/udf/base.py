@@ -1092,7 +1092,7 @@ class UDFPartRunner:
                 method == UDFMethod.TILE and getattr(
                     udf, 'ACCEPTS_CSR_VIEWS' if getattr(data, 'is_csr', False) else 'ACCEPTS_ROW_VIEWS', False)):
             # a region of interest as a row list over the resident frames, or sparse frames as a view of
-            # their CSR triple: only the mask operators read through it, everyone else gets the gathered /
+            # their CSR triple: only the UDFs that say so read through it, everyone else gets the gathered /
             # densified frames (once per tile)
             data = data.materialize()
         if method == UDFMethod.TILE:

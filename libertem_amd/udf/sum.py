@@ -20,6 +20,7 @@ class SumUDF(UDF):
     """
 
     REUSE_TASK_INSTANCES = True      # (udf/base.py: per-partition instances kept between runs)
+    ACCEPTS_CSR_VIEWS = True         # process_tile sums integer sparse frames through their CSR triple (no dense copy)
 
     def __init__(self, dtype='float32'):
         super().__init__(dtype=dtype)
@@ -93,7 +94,19 @@ class SumUDF(UDF):
         sl = SigSlice(view, self.meta.dataset_shape.sig)
         n_px = sl.n_px
         device = tile.device
-        if getattr(self.meta, 'corrections_folded', False) and self.meta.tiling_scheme_idx == 0:
+        folded = getattr(self.meta, 'corrections_folded', False)
+        if getattr(tile, 'is_csr', False):
+            # sparse frames as a view of their CSR triple (whole frames): integer data is summed per pixel in
+            # int64 from the stored entries alone -- exact -- and added into a float result; float data keeps the
+            # dense kernels' summation order, every other result dtype their arithmetic: the densified frames
+            if tile.dtype.kind in 'iu' and odt in (np.dtype(np.float32), np.dtype(np.float64)) and not folded \
+                    and sl.whole_frames:
+                ws = self.task_data.workspace.ptr(device, hip.csr_sum_frames_workspace(n_px))
+                hip.csr_sum_frames(device, tile.indptr_ptr(), tile.indices_ptr(), tile.values_ptr(), tile.dtype,
+                                   tile.rows_ptr(), tile.row0, n, n_px, out.data_ptr(), odt, True, ws)
+                return
+            tile = tile.materialize()
+        if folded and self.meta.tiling_scheme_idx == 0:
             self.results.n_raw[:] += n                  # once per group of frames (first sig slice)
         ws = self.task_data.workspace.ptr(device, hip.sum_frames_workspace(n, n_px, odt))
         if sl.whole_rows:

@@ -11,6 +11,7 @@ from libertem_amd.udf.device import check_device_args, runs_on_hip
 
 class SumSigUDF(UDF):
     REUSE_TASK_INSTANCES = True      # (udf/base.py: per-partition instances kept between runs)
+    ACCEPTS_CSR_VIEWS = True         # process_tile sums sparse frames through their CSR triple (no dense copy)
 
     def get_backends(self):
         # BACKEND_HIP on an MI355X worker, plain NumPy on a CPU executor (see SumUDF.get_backends)
@@ -52,6 +53,15 @@ class SumSigUDF(UDF):
             raise NotImplementedError(f"SumSigUDF: result dtype {out.dtype} not supported")
         n = tile.shape[0]
         accumulate = not self.results.get_buffer('intensity').write_once
+        if getattr(tile, 'is_csr', False):
+            # sparse frames as a view of their CSR triple (whole frames): the sum of a frame is the sum of its
+            # stored entries; complex results and the folded-corrections engine take the densified frames
+            if self.task_data.engine is None and out.dtype in (np.dtype(np.float32), np.dtype(np.float64)):
+                hip.csr_sum_sig(tile.device, tile.indptr_ptr(), tile.indices_ptr(), tile.values_ptr(), tile.dtype,
+                                tile.rows_ptr(), tile.row0, n, prod(tile.shape[1:]), out.data_ptr(), out.dtype,
+                                accumulate, stream=self.meta.stream_ptr)
+                return
+            tile = tile.materialize()
         if self.task_data.engine is not None:
             self.task_data.engine.process_tile(tile, out=out.reshape((n, 1)), accumulate=accumulate)
             return
