@@ -454,6 +454,25 @@ int ltmi_frms6_decode(int device, const void *src, int64_t frame_stride, int64_t
  * "" before the first.  A call that launches nothing leaves the string as it was. */
 const char *ltmi_frms6_last_kernel(void);
 
+/* Frame records gathered on the device: the payloads of a file of fixed-size records [frame header | pixels |
+ * frame footer] (Norpix .seq, EMPAD .raw, NanoMegas .blo) moved into one contiguous array.  `src`: DEVICE address of
+ * the first frame's PAYLOAD in a copy of (part of) the file -- the caller has added the file header and the frame
+ * header; the payload of frame i is the `payload_bytes` bytes at src + i * record_stride.  dst: DEVICE,
+ * contiguous, frame i at dst + i * payload_bytes.  Bytes are moved, not converted.  No byte outside the payloads
+ * is read and none outside [dst, dst + n_frames * payload_bytes) is written: the last record may end with its
+ * payload, the first may start the buffer.  One kernel k_records<W>, a lane moving W bytes per access; W is the
+ * largest of 16, 8, 4, 2, 1 that divides the address src, record_stride, payload_bytes and the address dst
+ * (chosen here, on the host; no realignment that reads around a payload).  Frames are not a grid dimension and
+ * all offsets are 64-bit: any number of frames, records any distance apart.  n_frames == 0 launches nothing.
+ * n_frames < 0, payload_bytes < 1 and record_stride < payload_bytes: LTMI_E_SHAPE.  Replaces the per-tile read
+ * ranges with which the reference strips frame headers and footers on the host
+ * (src/libertem/io/dataset/base/tiling.py, decode.py). */
+int ltmi_records_gather(int device, const void *src, int64_t record_stride, int64_t n_frames,
+                        int64_t payload_bytes, void *dst, void *stream);
+/* Which kernel the calling thread's last ltmi_records_gather launched: "k_records<16>" ... "k_records<1>"; ""
+ * before the first.  A call that launches nothing leaves the string as it was. */
+const char *ltmi_records_last_kernel(void);
+
 /* Centre-of-mass post-processing on a 2D scan of ny x nx positions: from the rows (sum, sum*y, sum*x)
  * of the 3-mask product to the shift field and its derived maps, float64.  Replaces the NumPy chain
  * center_shifts -> apply_correction -> magnitude / divergence / curl_2d of src/libertem/udf/com.py:
