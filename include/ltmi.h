@@ -473,6 +473,27 @@ int ltmi_records_gather(int device, const void *src, int64_t record_stride, int6
  * before the first.  A call that launches nothing leaves the string as it was. */
 const char *ltmi_records_last_kernel(void);
 
+/* Out-of-place transposition on the device: dst[c * ld_dst + r] = src[r * ld_src + c] for r < rows, c < cols.
+ * src, dst: DEVICE, element-aligned (16-byte elements: 8), not overlapping; ld_src >= cols and ld_dst >= rows, in
+ * elements.  Elements of item_bytes = 1, 2, 4, 8 or 16 bytes are moved, never interpreted (any dtype of that size,
+ * complex128 included).  One kernel k_transpose<item_bytes>: a workgroup stages one tile (128 x 128 elements at 1
+ * and 2 bytes, 64 x 64 at 4 and 8, 32 x 32 at 16) through an XOR-swizzled LDS image per step, so the global reads
+ * run along the rows of src and the global writes along the rows of dst, 128 B to 512 B per row segment; edge tiles
+ * are predicated.  Tiles are walked with a grid stride and all offsets are 64-bit: no grid dimension bounds rows or
+ * cols.  No byte of dst outside the cols x rows rectangle is written (not the padding between rows and ld_dst
+ * either) and none of src outside the rows x cols rectangle is read.  2 * rows * cols * item_bytes bytes of HBM
+ * traffic.  rows == 0 or cols == 0 launches nothing.  Negative sizes and null pointers with work to do:
+ * LTMI_E_INVALID; ld_src < cols, ld_dst < rows and sizes whose byte span does not fit int64: LTMI_E_SHAPE; any
+ * other item_bytes: LTMI_E_DTYPE.  Replaces the `partition.T` assignment into the memory map of
+ * ConvertTransposedDatasetUDF.process_partition (src/libertem/contrib/convert_transposed.py:28-40), which the
+ * reference runs on one CPU thread per partition. */
+int ltmi_transpose2d(int device, const void *src, int64_t ld_src, int64_t rows, int64_t cols, int item_bytes,
+                     void *dst, int64_t ld_dst, void *stream);
+/* Which kernel the calling thread's last ltmi_transpose2d launched: "k_transpose<1>" ... "k_transpose<16>"; ""
+ * before the first.  A call that launches nothing leaves the string as it was.  (Names the instantiation behind
+ * src/libertem/contrib/convert_transposed.py:28-40.) */
+const char *ltmi_transpose_last_kernel(void);
+
 /* Centre-of-mass post-processing on a 2D scan of ny x nx positions: from the rows (sum, sum*y, sum*x)
  * of the 3-mask product to the shift field and its derived maps, float64.  Replaces the NumPy chain
  * center_shifts -> apply_correction -> magnitude / divergence / curl_2d of src/libertem/udf/com.py:

@@ -34,7 +34,7 @@ EXPORTS = (
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
     'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
     'ltmi_logsum_frames',
-    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_records_gather', 'ltmi_records_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
+    'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_records_gather', 'ltmi_records_last_kernel', 'ltmi_transpose2d', 'ltmi_transpose_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
@@ -280,6 +280,9 @@ def lib():
         L.ltmi_records_gather.argtypes = [i32, vp, i64, i64, i64, vp, vp]
         L.ltmi_records_last_kernel.argtypes = []
         L.ltmi_records_last_kernel.restype = c.c_char_p
+        L.ltmi_transpose2d.argtypes = [i32, vp, i64, i64, i64, i32, vp, i64, vp]
+        L.ltmi_transpose_last_kernel.argtypes = []
+        L.ltmi_transpose_last_kernel.restype = c.c_char_p
         L.ltmi_mib_last_kernel.restype = c.c_char_p
         L.ltmi_com_fields.argtypes = [i32, vp, i64, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp,
                                       vp, vp, vp, vp, vp]
@@ -865,6 +868,21 @@ def records_last_kernel():
     """Name of the kernel this thread's last `records_gather` launched: 'k_records<16>' ... 'k_records<1>' (the
     bytes a lane moves per access); '' before the first."""
     return lib().ltmi_records_last_kernel().decode()
+
+
+def transpose2d(device, src_ptr, ld_src, rows, cols, item_bytes, dst_ptr, ld_dst, stream=None):
+    """dst[c * ld_dst + r] = src[r * ld_src + c] for r < rows, c < cols, in HBM; elements of `item_bytes` (1, 2, 4,
+    8, 16) bytes are moved, not converted, `ld_src` / `ld_dst` in elements.  Nothing outside the cols x rows
+    rectangle of dst is written."""
+    check(lib().ltmi_transpose2d(
+        int(device), src_ptr, int(ld_src), int(rows), int(cols), int(item_bytes), dst_ptr, int(ld_dst),
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_transpose2d')
+
+
+def transpose_last_kernel():
+    """Name of the kernel this thread's last `transpose2d` launched: 'k_transpose<1>' ... 'k_transpose<16>' (the
+    item size); '' before the first."""
+    return lib().ltmi_transpose_last_kernel().decode()
 
 
 def com_fields(device, raw_ptr, ld_raw, ny, nx, ref_y, ref_x, transform, out_y, out_x, out_mag=None,

@@ -34,7 +34,10 @@ class RawFileDataSet(MemoryDataSet):
 
     def __init__(self, path, dtype, scan_size=None, detector_size=None, enable_direct=False,
                  detector_size_raw=None, crop_detector_to=None, tileshape=None, nav_shape=None,
-                 sig_shape=None, sync_offset=0, io_backend=None, num_partitions=None, shard=None):
+                 sig_shape=None, sync_offset=0, io_backend=None, num_partitions=None, shard=None,
+                 _data_offset=0):
+        # `_data_offset` (internal): the frames start that many bytes into the file (the header of a .npy file,
+        # io/dataset/npy.py)
         # `io_backend` / `enable_direct` choose HOW the reference reads the file (mmap, buffered, O_DIRECT); here the
         # file is always memory-mapped and its frames go to the GPU through the upload stager: accepted, not used
         if enable_direct and io_backend is not None:
@@ -74,7 +77,7 @@ class RawFileDataSet(MemoryDataSet):
         dt = np.dtype(dtype)
         self._path = path
         try:
-            filesize = os.stat(path).st_size
+            filesize = max(0, os.stat(path).st_size - int(_data_offset))
         except OSError as e:
             raise DataSetException(f"could not open file {path}: {e}")
         frame_bytes = prod(sig_shape) * dt.itemsize
@@ -90,7 +93,7 @@ class RawFileDataSet(MemoryDataSet):
         lead_blank = max(0, -sync_offset)
         avail = max(0, min(n_file - skip, n_nav - lead_blank))
         if avail > 0:
-            mm = np.memmap(path, dtype=dt, mode='r', offset=skip * frame_bytes,
+            mm = np.memmap(path, dtype=dt, mode='r', offset=int(_data_offset) + skip * frame_bytes,
                            shape=(avail,) + sig_shape)
         else:
             mm = np.zeros((0,) + sig_shape, dtype=dt)

@@ -5,7 +5,9 @@ from .base import (
 from libertem_amd.common.udf import UDFMethod
 from libertem_amd.common.exceptions import UDFRunCancelled, UDFException
 from .auto import AutoUDF
+from .record import RecordUDF
 
 __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPostprocessMixin', 'UDFPreprocessMixin',
            'UDFMergeAllMixin', 'UDFMeta', 'UDFRunner', 'UDFData', 'NoOpUDF', 'UDFMethod', 'check_cast', 'AutoUDF',
+           'RecordUDF',
            'UDFRunCancelled', 'UDFException']
