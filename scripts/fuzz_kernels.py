@@ -157,6 +157,8 @@ for case in range(n_cases):
             handle.set_tuning(mt=0, waves=0, ksplit=ksplit)
         base = gen(rd if rd.kind in 'iu' else 'float32', (n_frames, n_masks)).astype(rd)
         out = dev(base.copy())
+        if tdt.kind == 'f':
+            data[:, n_px:] = np.nan             # row padding no kernel may read: 0 * NaN would show (every `gen` above)
         t = dev(data)
         desc = (kind, n_frames, n_px, ld, n_masks, str(tdt), str(rd), accumulate, ksplit)
         if kind == 'shift':
