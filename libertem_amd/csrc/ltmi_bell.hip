@@ -1446,8 +1446,9 @@ __global__ void k_bell_tail(const T *__restrict__ tile, int64_t ld, int64_t n_fr
 }
 
 template <typename T, int TL>
-static int launch_bell_t(ltmi_masks *m, BellImage *b, const T *tile, int64_t n_frames, int64_t ld,
-                         float *out, int64_t ld_out_f, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_bell_t(ltmi_masks *m, BellImage *b, const MaskCall &call, int n_cols) {   // call.ld_out in floats
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
     using C = BeCfg<T, TL>;
     auto kern = k_bell_apply<T, TL>;
     static bool set[16] = {false};
@@ -1456,26 +1457,26 @@ static int launch_bell_t(ltmi_masks *m, BellImage *b, const T *tile, int64_t n_f
                                      C::LDS_BYTES));
         set[m->device & 15] = true;
     }
-    dim3 grid((unsigned)((n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
+    dim3 grid((unsigned)((call.n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
     const char *abl = getenv("LTMI_BELL_ABLATE");    // 1: no frame DMA, 2: no records (bench only)
     const int ablate = abl ? atoi(abl) : 0;
     unsigned long long *prof = nullptr;
 #ifdef BE_PROF
     static unsigned long long *prof_dev = nullptr;
     if (!prof_dev) LTMI_HIP(hipMalloc((void **)&prof_dev, 8 * sizeof(unsigned long long)));
-    LTMI_HIP(hipMemsetAsync(prof_dev, 0, 8 * sizeof(unsigned long long), stream));
+    LTMI_HIP(hipMemsetAsync(prof_dev, 0, 8 * sizeof(unsigned long long), call.stream));
     prof = prof_dev;
 #endif
-    hipLaunchKernelGGL(kern, grid, dim3(BE_SETS * 64), C::LDS_BYTES, stream, tile, ld, n_frames,
+    hipLaunchKernelGGL(kern, grid, dim3(BE_SETS * 64), C::LDS_BYTES, call.stream, tile, call.ld_tile, call.n_frames,
                        m->n_px, (const uint32_t *)b->stream, (const int64_t *)b->stream_off,
                        (const int *)b->nblk, (const int *)b->active,
                        (const int *)b->active_off, out,
-                       ld_out_f, n_cols, accumulate, ablate, prof, m->roi_rows);
+                       call.ld_out, n_cols, call.accumulate, ablate, prof, call.rows);
     LTMI_HIP(hipGetLastError());
 #ifdef BE_PROF
     {
         unsigned long long h[8];
-        LTMI_HIP(hipStreamSynchronize(stream));
+        LTMI_HIP(hipStreamSynchronize(call.stream));
         LTMI_HIP(hipMemcpy(h, prof_dev, sizeof(h), hipMemcpyDeviceToHost));
         const double w = (double)h[7];
         fprintf(stderr, "BE_PROF cycles per wave (%.0f waves, ~%.0f records each): record-wait %.0f  "
@@ -1485,21 +1486,23 @@ static int launch_bell_t(ltmi_masks *m, BellImage *b, const T *tile, int64_t n_f
     }
 #endif
     if (b->n_tail > 0) {
-        hipLaunchKernelGGL(k_bell_tail<T>, dim3((unsigned)((n_frames + 255) / 256), (unsigned)std::min(b->n_tail_cols, 65535)),
-                           dim3(256), 0, stream, tile, ld, n_frames, (const int32_t *)b->tail_px,
-                           (const int32_t *)b->tail_col, (const float *)b->tail_val,
-                           (const int32_t *)b->tail_seg, (int)b->n_tail_cols, out, ld_out_f, m->roi_rows);
+        hipLaunchKernelGGL(k_bell_tail<T>, dim3((unsigned)((call.n_frames + 255) / 256),
+                           (unsigned)std::min(b->n_tail_cols, 65535)), dim3(256), 0, call.stream, tile, call.ld_tile,
+                           call.n_frames, (const int32_t *)b->tail_px, (const int32_t *)b->tail_col,
+                           (const float *)b->tail_val, (const int32_t *)b->tail_seg, (int)b->n_tail_cols, out,
+                           call.ld_out, call.rows);
         LTMI_HIP(hipGetLastError());
     }
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_bell_apply<%s,tiles=%d%s> grid=(%u,%u) blocks=%zu x%.2f crit=%ld", typeid(T).name(), TL,
-             m->roi_rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->mac_ratio, b->crit_records);
+             call.rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->mac_ratio, b->crit_records);
     return LTMI_OK;
 }
 
 template <typename T, int TL>
-static int launch_bell_flat(ltmi_masks *m, BellImage *b, const T *tile, int64_t n_frames, int64_t ld,
-                            float *out, int64_t ld_out_f, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_bell_flat(ltmi_masks *m, BellImage *b, const MaskCall &call, int n_cols) {
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
     using C = BeCfg<T, TL, BE_FP>;
     auto kern = k_bell_flat<T, TL>;
     constexpr int LDS = BE_FNBUF * C::BUF;
@@ -1508,25 +1511,26 @@ static int launch_bell_flat(ltmi_masks *m, BellImage *b, const T *tile, int64_t 
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         set[m->device & 15] = true;
     }
-    dim3 grid((unsigned)((n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
+    dim3 grid((unsigned)((call.n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
     const char *abl = getenv("LTMI_BELL_ABLATE");
     const int ablate = abl ? atoi(abl) : 0;
-    hipLaunchKernelGGL(kern, grid, dim3(BE_SETS * 64), LDS, stream, tile, ld, n_frames, m->n_px,
+    hipLaunchKernelGGL(kern, grid, dim3(BE_SETS * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                        (const uint32_t *)b->stream, (const int64_t *)b->stream_off,
                        (const uint32_t *)b->ctrl, (const int64_t *)b->ctrl_off, (const int *)b->n_rec,
-                       (const int *)b->active, (const int *)b->active_off, out, ld_out_f, n_cols,
-                       accumulate, ablate, m->roi_rows, (const float *)b->inv_scale);
+                       (const int *)b->active, (const int *)b->active_off, out, call.ld_out, n_cols,
+                       call.accumulate, ablate, call.rows, (const float *)b->inv_scale);
     LTMI_HIP(hipGetLastError());
     if (b->n_tail > 0) {
-        hipLaunchKernelGGL(k_bell_tail<T>, dim3((unsigned)((n_frames + 255) / 256), (unsigned)std::min(b->n_tail_cols, 65535)),
-                           dim3(256), 0, stream, tile, ld, n_frames, (const int32_t *)b->tail_px,
-                           (const int32_t *)b->tail_col, (const float *)b->tail_val,
-                           (const int32_t *)b->tail_seg, (int)b->n_tail_cols, out, ld_out_f, m->roi_rows);
+        hipLaunchKernelGGL(k_bell_tail<T>, dim3((unsigned)((call.n_frames + 255) / 256),
+                           (unsigned)std::min(b->n_tail_cols, 65535)), dim3(256), 0, call.stream, tile, call.ld_tile,
+                           call.n_frames, (const int32_t *)b->tail_px, (const int32_t *)b->tail_col,
+                           (const float *)b->tail_val, (const int32_t *)b->tail_seg, (int)b->n_tail_cols, out,
+                           call.ld_out, call.rows);
         LTMI_HIP(hipGetLastError());
     }
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_bell_flat<%s,tiles=%d,f16%s> grid=(%u,%u) blocks=%zu x%.2f crit=%ld tail=%d", typeid(T).name(), TL,
-             m->roi_rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->mac_ratio, b->crit_records, b->n_tail);
+             call.rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->mac_ratio, b->crit_records, b->n_tail);
     return LTMI_OK;
 }
 
@@ -1535,51 +1539,45 @@ static int launch_bell_flat(ltmi_masks *m, BellImage *b, const T *tile, int64_t 
 // per workgroup take 1.65 - 1.8x the time of 32 (profiles/r02_sparse_experiments.txt) -- but make fewer, longer workgroups: whichever needs the
 // shorter sequence of rounds on the 256 CUs (LTMI_BELL_TILES forces one).
 template <typename T>
-static int launch_bell(ltmi_masks *m, BellImage *b, const T *tile, int64_t n_frames, int64_t ld,
-                       float *out, int64_t ld_out_f, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_bell(ltmi_masks *m, BellImage *b, const MaskCall &call, int n_cols) {
     constexpr int LO = sizeof(T) == 4 ? 1 : 2, HI = 2 * LO;
     static const int forced = getenv("LTMI_BELL_TILES") ? atoi(getenv("LTMI_BELL_TILES")) : 0;
-    auto rounds = [&](int tl) { return (double)(((n_frames + 16 * tl - 1) / (16 * tl) + 255) / 256); };
+    auto rounds = [&](int tl) { return (double)(((call.n_frames + 16 * tl - 1) / (16 * tl) + 255) / 256); };
     const bool hi = forced ? forced == HI : rounds(HI) * 1.7 < rounds(LO);
     // k_bell_apply with four tiles has one accumulation level only: not for columns of more than 2048 stored values
     const bool hi_apply = forced ? hi : (hi && (HI <= 2 || b->max_col_entries <= 2048));
     if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) {
         if (b->h16) {               // 1- / 2-byte integer pixels (signed ones since round 6): the float16 image
-            if (hi)
-                return launch_bell_flat<T, HI>(m, b->h16, tile, n_frames, ld, out, ld_out_f, n_cols,
-                                               accumulate, stream);
-            return launch_bell_flat<T, LO>(m, b->h16, tile, n_frames, ld, out, ld_out_f, n_cols,
-                                           accumulate, stream);
+            if (hi) return launch_bell_flat<T, HI>(m, b->h16, call, n_cols);
+            return launch_bell_flat<T, LO>(m, b->h16, call, n_cols);
         }
     }
-    if (hi_apply)
-        return launch_bell_t<T, HI>(m, b, tile, n_frames, ld, out, ld_out_f, n_cols, accumulate, stream);
-    return launch_bell_t<T, LO>(m, b, tile, n_frames, ld, out, ld_out_f, n_cols, accumulate, stream);
+    if (hi_apply) return launch_bell_t<T, HI>(m, b, call, n_cols);
+    return launch_bell_t<T, LO>(m, b, call, n_cols);
 }
 
 // handled = false: the tile does not meet the kernel's rules (caller uses the SELL kernel)
-int bell_apply(ltmi_masks *m, void *image, int cplx, const void *tile, int tile_dtype,
-               int64_t n_frames, int64_t ld_tile, void *out, int64_t ld_out, int accumulate,
-               hipStream_t stream, bool *handled) {
+int bell_apply(ltmi_masks *m, void *image, int cplx, const MaskCall &call, bool *handled) {
     BellImage *b = (BellImage *)image;
+    const int tile_dtype = call.tile_dtype;
     const int sz = dtype_size(tile_dtype);
     *handled = false;
-    if (!b || n_frames <= 0) return LTMI_OK;
+    if (!b || call.n_frames <= 0) return LTMI_OK;
     // rows of any element alignment (LDS-DMA reads them); a partial last 16-byte piece of a row is not
     // fetched -- its pixels (< 16) are k_bell_tail's
-    if (sz <= 0 || !vector_loads_ok(tile, ld_tile, (size_t)sz)) return LTMI_OK;
+    if (sz <= 0 || !vector_loads_ok(call.tile, call.ld_tile, (size_t)sz)) return LTMI_OK;
     const int nc = cplx ? 2 : 1;
     const int n_cols = (int)(m->n_masks * nc);
-    float *o = (float *)out;
-    const int64_t ldo = ld_out * nc;
+    MaskCall f32 = call;
+    f32.ld_out = call.ld_out * nc;
     *handled = true;
     switch (tile_dtype) {
         case LTMI_BOOL:
-        case LTMI_U8: return launch_bell<uint8_t>(m, b, (const uint8_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_I8: return launch_bell<int8_t>(m, b, (const int8_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_U16: return launch_bell<uint16_t>(m, b, (const uint16_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_I16: return launch_bell<int16_t>(m, b, (const int16_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_F32: return launch_bell<float>(m, b, (const float *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
+        case LTMI_U8: return launch_bell<uint8_t>(m, b, f32, n_cols);
+        case LTMI_I8: return launch_bell<int8_t>(m, b, f32, n_cols);
+        case LTMI_U16: return launch_bell<uint16_t>(m, b, f32, n_cols);
+        case LTMI_I16: return launch_bell<int16_t>(m, b, f32, n_cols);
+        case LTMI_F32: return launch_bell<float>(m, b, f32, n_cols);
     }
     *handled = false;
     return LTMI_OK;

@@ -79,6 +79,13 @@ static inline int choose_ksplit(int64_t wgs, int n_slots) {
     return best_ks;
 }
 
+// every part of a split of n slots into ksplit parts owns at least one slot: the smallest number of parts of the
+// same size per part
+static inline int clamp_ksplit(int ksplit, int n) {
+    const int per = (n + ksplit - 1) / ksplit;
+    return (n + per - 1) / per;
+}
+
 static inline int dtype_size(int dt) {
     switch (dt) {
         case LTMI_BOOL: case LTMI_U8: case LTMI_I8: return 1;
@@ -99,14 +106,27 @@ static inline const char *dtype_name(int dt) {
 struct cfloat { float re, im; };
 struct cdouble { double re, im; };
 
+// one mask product: out[i, k] (+)= sum_p tile[i, p] * masks[k, p] for n_frames frames -- with `rows` (a device list,
+// ltmi_apply_masks_rows) result row i is frame rows[i] of the tile
+struct MaskCall {
+    const void *tile;
+    int tile_dtype;
+    int64_t n_frames, ld_tile;
+    void *out;
+    int64_t ld_out;
+    int accumulate;
+    hipStream_t stream;
+    const int32_t *rows = nullptr;
+};
+
 }  // namespace ltmi
 
 struct ltmi_masks;
 namespace ltmi {
 int dense64_create(ltmi_masks *m);
 void dense64_destroy(ltmi_masks *m);
-int dense64_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld,
-                  void *out, int64_t ld_out, int accumulate, hipStream_t stream, bool *handled);
+// (img64: the handle's image or that of the shifted stack)
+int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool *handled);
 bool dense64_rows_ok(const ltmi_masks *m, const void *tile, int tile_dtype, int64_t ld);
 size_t dense64_image_bytes(const ltmi_masks *m);
 int dense64_build_shifted(ltmi_masks *m, int sig_h, int sig_w, int dy, int dx, double *img,
@@ -122,8 +142,7 @@ double scat_fill(const int64_t *indptr, const int64_t *indices, int nc, int64_t 
 void *scat_build(const int64_t *indptr, const int64_t *indices, const float *vals, int nc, int64_t n_px,
                  int64_t n_masks, int *err);
 void scat_destroy(void *set);
-int scat_apply(ltmi_masks *m, void *set, int cplx, const void *tile, int tile_dtype, int64_t n_frames,
-               int64_t ld_tile, void *out, int64_t ld_out, int accumulate, hipStream_t stream, bool *handled);
+int scat_apply(ltmi_masks *m, void *set, int cplx, const MaskCall &call, bool *handled);
 // float32 frames x multi-group float32 stacks on the bf16 matrix cores, float32-accurate (ltmi_split.hip)
 bool split_selected(bool tuned);
 bool split_wanted(int n_cols, int64_t n_px);
@@ -131,8 +150,7 @@ int split_create(int device, const float *gmasks, int64_t n_masks, int cpm, int6
                  void **image);
 void split_destroy(void *image);
 size_t split_image_bytes(const void *image);
-int split_apply(ltmi_masks *m, void *image, const float *tile, int64_t n_frames, int64_t ld, float *out,
-                int64_t ld_out, int accumulate, hipStream_t stream);
+int split_apply(ltmi_masks *m, void *image, const MaskCall &call);
 // CrystallinityUDF for 256 x 256 frames in one kernel (ltmi_cryst.hip)
 int cryst_fused_max_cols();
 bool cryst_fused_shape(int h, int w);
@@ -146,8 +164,7 @@ int cryst_fused(const void *tile, int tile_dtype, int64_t n_frames, int64_t ld, 
 int fold_create(ltmi_masks *m, int sig_h, int sig_w);
 void fold_destroy(ltmi_masks *m);
 bool fold_takes(const ltmi_masks *m, const float *tile, int64_t ld);
-int launch_fold(ltmi_masks *m, const float *tile, int64_t n_frames, int64_t ld, float *out, int64_t ld_out,
-                int accumulate, hipStream_t stream);
+int launch_fold(ltmi_masks *m, const MaskCall &call);
 // banded sparse stacks (column blocks with a common support each: radial Fourier with several bins) on k_dense_fold
 struct KeptCsr;                                                             // host copy of a CSR stack, rows sorted
 KeptCsr *band_keep_csr(const int64_t *indptr, const int64_t *indices, const float *vals, int nc, int64_t n_px,
@@ -156,11 +173,9 @@ void band_free_csr(KeptCsr *k);
 void *band_build(const KeptCsr *k, int sig_h, int sig_w, double other_macs);    // nullptr: the other kernels serve
 void band_destroy(void *band);
 bool band_takes(void *band, const ltmi_masks *m, const void *tile, int tile_dtype, int64_t ld);   // float32, 1- / 2-byte integers
-int band_apply(ltmi_masks *m, void *band, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld, float *out,
-               int64_t ld_out, int n_cols, int accumulate, hipStream_t stream);
+int band_apply(ltmi_masks *m, void *band, const MaskCall &call, int n_cols);
 bool fold_takes16(ltmi_masks *m, const void *tile, int64_t ld, int px_bytes);   // 1- / 2-byte integer frames (image built on first use)
-int launch_fold16(ltmi_masks *m, const void *tile, int px_bytes, bool is_signed, int64_t n_frames, int64_t ld,
-                  float *out, int64_t ld_out, int accumulate, hipStream_t stream);
+int launch_fold16(ltmi_masks *m, const MaskCall &call, int px_bytes, bool is_signed);
 // the K-split workspace of a dense handle (ltmi_dense.hip)
 int dense_ensure_partials(ltmi_masks *m, size_t need, hipStream_t stream);
 float *dense_partial_sums(const ltmi_masks *m);
@@ -175,12 +190,10 @@ int cryst_fused_corrected(const void *tile, int tile_dtype, int64_t n_frames, in
                           int n_cols, float *mask_t, void *gbuf, int64_t gbuf_frames, void *ws, float *out,
                           int accumulate, int n_cu, hipStream_t stream, bool *handled);
 // non-finite pixels on sparse stacks (ltmi_guard.hip; the gather-kernel redo: ltmi_sparse.hip)
-int csr_redo(ltmi_masks *m, const void *tile, int tile_dtype, int64_t max_frames, int64_t ld_tile, void *out,
-             int64_t ld_out, const int32_t *sel, const int *n_sel, const int32_t *roi_rows, hipStream_t stream);
+int csr_redo(ltmi_masks *m, const MaskCall &call, const int32_t *sel, const int *n_sel);   // call.n_frames: at most
 bool csr_is_f64(const ltmi_masks *m);
 bool guard_wanted(const ltmi_masks *m, int tile_dtype);
-int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, void *out,
-                int64_t ld_out, int accumulate, hipStream_t stream);
+int guard_apply(ltmi_masks *m, const MaskCall &call);
 void guard_destroy(ltmi_masks *m);
 // the guard's pieces, for the shifted routes of ltmi_dense.hip: where the product goes, which result rows are
 // non-finite (lists on the device), the product to its place
@@ -191,13 +204,10 @@ int guard_list_rows(ltmi_masks *m, const void *target, int64_t ld_target, int64_
                     int **ctl, int32_t **list);
 int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, int accumulate, hipStream_t stream);
 // ltmi_apply_masks without the guard (ltmi_dense.hip)
-int apply_masks_unguarded(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
-                          void *out, int64_t ld_out, int accumulate, hipStream_t stream);
+int apply_masks_unguarded(ltmi_masks *m, const MaskCall &call);
 // sparse frames against a dense stack (ltmi_csrframes.hip): the pixel-major image of the handle
 void csrframes_destroy(ltmi_masks *m);
-int bell_apply(ltmi_masks *m, void *image, int cplx, const void *tile, int tile_dtype,
-               int64_t n_frames, int64_t ld_tile, void *out, int64_t ld_out, int accumulate,
-               hipStream_t stream, bool *handled);
+int bell_apply(ltmi_masks *m, void *image, int cplx, const MaskCall &call, bool *handled);
 }  // namespace ltmi
 
 // The opaque handle behind `ltmi_masks*` (shared by ltmi_dense.hip and ltmi_sparse.hip).
@@ -228,7 +238,6 @@ struct ltmi_masks {
     int32_t *tail_px = nullptr, *tail_col = nullptr;
     float *tail_val = nullptr;
     int tail_n = 0;
-    bool x16_used = false;
     // float64 results on the f64 matrix cores (ltmi_dense64.hip)
     double *img64 = nullptr;
     int n_groups64 = 0, n_chunks64 = 0;
@@ -243,9 +252,6 @@ struct ltmi_masks {
     float *partials = nullptr;
     size_t partials_bytes = 0;
     int tune_mt = 0, tune_waves = 0, tune_ksplit = 0, tune_ksplit_ring = 0;
-    // ltmi_apply_masks_rows: device list of the tile's frames to multiply (result row i = frame rows[i]);
-    // set for the duration of that call only
-    const int32_t *roi_rows = nullptr;
     // kind 0 and 1
     void *gmasks = nullptr;  // (n_masks, n_px) of the accumulate type
     // ltmi_apply_masks_csr: the stack again pixel-major, [n_px][m_pad_px] of float / double, built on first use

@@ -1382,8 +1382,7 @@ int csr_destroy(ltmi_masks *m);   // ltmi_sparse.hip
 int csr_set_sig_shape(ltmi_masks *m, int sig_h, int sig_w);
 bool csr_has_band(const ltmi_masks *m);
 bool csr_rows_ok(const ltmi_masks *m, const void *tile, int tile_dtype, int64_t ld_tile);
-int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
-              void *out, int64_t ld_out, int accumulate, hipStream_t stream);
+int csr_apply(ltmi_masks *m, const MaskCall &call);
 }
 
 static bool mfma_tile_dtype(int dt) {
@@ -1737,15 +1736,20 @@ extern "C" int ltmi_masks_set_tuning(ltmi_masks *m, int mt, int waves, int kspli
         m->tune_waves = 0;
         m->tune_ksplit = ksplit;
         m->tune_ksplit_ring = waves;
-        return LTMI_OK;
+    } else {
+        if (!(mt == 0 || mt == 1 || mt == 2) || !(waves == 0 || waves == 4 || waves == 8) || ksplit < 0)
+            LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_set_tuning: unsupported (mt=%d waves=%d ksplit=%d)",
+                      mt, waves, ksplit);
+        m->tune_mt = mt;
+        m->tune_waves = waves;
+        m->tune_ksplit = ksplit;
+        m->tune_ksplit_ring = 0;
     }
-    if (!(mt == 0 || mt == 1 || mt == 2) || !(waves == 0 || waves == 4 || waves == 8) || ksplit < 0)
-        LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_set_tuning: unsupported (mt=%d waves=%d ksplit=%d)",
-                  mt, waves, ksplit);
-    m->tune_mt = mt;
-    m->tune_waves = waves;
-    m->tune_ksplit = ksplit;
-    m->tune_ksplit_ring = 0;
+    // (the column blocks of a wide stack run only while mt = waves = 0: the split and the code are theirs too)
+    for (ltmi_masks *b : m->blocks) {
+        b->tune_ksplit = m->tune_ksplit;
+        b->tune_ksplit_ring = m->tune_ksplit_ring;
+    }
     return LTMI_OK;
 }
 
@@ -1788,9 +1792,7 @@ static inline int *partial_counters(const ltmi_masks *m, int64_t n_blocks) {
 }
 
 template <typename T, int MT, int NG, int WAVES, bool ALIGNED>
-static int launch_mfma_variant(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld,
-                               float *out, int64_t ld_out, int accumulate, int ksplit,
-                               hipStream_t stream) {
+static int launch_mfma_variant(ltmi_masks *m, const MaskCall &call, int ksplit) {
     auto kern = k_dense_mfma<T, MT, NG, WAVES, ALIGNED>;
     const size_t lds_bytes = (size_t)2 * NG * CHUNK_FLOATS * sizeof(float);
     static bool attr_set[16] = {false};   // per device
@@ -1799,11 +1801,11 @@ static int launch_mfma_variant(ltmi_masks *m, const T *tile, int64_t n_frames, i
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         attr_set[m->device & 15] = true;
     }
-    dim3 grid((unsigned)((n_frames + WAVES * MT * 16 - 1) / (WAVES * MT * 16)), (unsigned)ksplit,
+    dim3 grid((unsigned)((call.n_frames + WAVES * MT * 16 - 1) / (WAVES * MT * 16)), (unsigned)ksplit,
               (unsigned)(m->n_groups / NG));
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds_bytes, stream, tile, ld, n_frames, m->n_px,
-                       (const float *)m->img, m->n_chunks, out, ld_out, m->n_cols, accumulate,
-                       partial_sums(m), ksplit);
+    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds_bytes, call.stream, (const T *)call.tile, call.ld_tile,
+                       call.n_frames, m->n_px, (const float *)m->img, m->n_chunks, (float *)call.out, call.ld_out,
+                       m->n_cols, call.accumulate, partial_sums(m), ksplit);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_dense_mfma<%s,MT=%d,NG=%d,WAVES=%d,%s> grid=(%u,%u,%u)", typeid(T).name(), MT, NG,
@@ -1815,11 +1817,12 @@ static int launch_mfma_variant(ltmi_masks *m, const T *tile, int64_t n_frames, i
 // (ltmi_masks_set_tuning waves code 34 = one tile / 8 waves, 35 = two tiles / 4 waves)
 // kernel instantiation point.  -DLTMI_DENSE_EXP (experiment builds, scripts/dense_variant.sh): only the
 // C5 kernels (float frames, 3 groups + 0 / 2 VALU columns) are compiled -- a minute instead of five
+template <typename T>
+using LdsKernel = void (*)(const T *, int64_t, int64_t, int64_t, const float *, int, float *, int64_t, int, int,
+                           float *, int, const int32_t *, const float *const *, int *, const float *, const float *,
+                           const int32_t *, const int32_t *, int);
 template <typename T, int NG, int ABL, int IND, int NE, int TILES, bool X16 = false>
-static auto lds_kernel() -> void (*)(const T *, int64_t, int64_t, int64_t, const float *, int, float *,
-                                     int64_t, int, int, float *, int, const int32_t *,
-                                     const float *const *, int *, const float *, const float *,
-                                     const int32_t *, const int32_t *, int) {
+static LdsKernel<T> lds_kernel() {
     // the timing-only ablations (tuning codes 31 / 32) and the one-tile-per-wave shape (34) exist for the
     // C2 kernel only -- uint16 pixels, one column group --: they are bench comparisons
     // (scripts/clock_probe.py, profiles/r02_tiles.txt), and every variant is minutes of compile time
@@ -1864,19 +1867,53 @@ static inline int lds_tiles(const ltmi_masks *m) {
     return m->tune_ksplit_ring == 34 ? 1 : 2;
 }
 
+// what the launches of k_dense_lds over a whole tile share: LDS size of the kernel (once per device and variant:
+// `attr_set`), split of the mask slots, the launch, the reduction of the partials; `name`: the kernel as
+// ltmi_masks_last_kernel reports it, the grid is appended
+template <typename T, typename CFG>
+static int launch_lds_kernel(ltmi_masks *m, const MaskCall &call, LdsKernel<T> kern, const float *img, int n_slots,
+                             int64_t gz, bool x16, bool *attr_set, const char *name) {
+    if (!*attr_set) {
+        LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     CFG::LDS_BYTES));
+        *attr_set = true;
+    }
+    const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
+    int ksplit = m->tune_ksplit;
+    if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, n_slots);
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, n_slots)), n_slots);
+    if (ksplit > 1) {
+        int rc = ensure_partials(m, (size_t)ksplit * call.n_frames * m->n_cols * sizeof(float), call.stream);
+        if (rc != LTMI_OK) return rc;
+    }
+    dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
+    int *kcount = ksplit > 1 ? partial_counters(m, gx * gz) : nullptr;
+    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, call.stream, (const T *)call.tile,
+                       call.ld_tile, call.n_frames, m->n_px, img, n_slots, (float *)call.out, call.ld_out, m->n_cols,
+                       call.accumulate, partial_sums(m), ksplit_order(ksplit), call.rows,
+                       (const float *const *)nullptr, kcount,
+                       x16 ? (const float *)m->inv_scale : (const float *)nullptr,
+                       (const float *)m->tail_val, (const int32_t *)m->tail_col, (const int32_t *)m->tail_px,
+                       x16 ? m->tail_n : 0);
+    LTMI_HIP(hipGetLastError());
+    int len = snprintf(m->last_kernel, sizeof(m->last_kernel), "%s grid=(%u,%u,%u)", name, grid.x, grid.y, grid.z);
+    if (x16 && m->tail_n > 0 && len < (int)sizeof(m->last_kernel))   // (small weights: the epilogue's float32 products)
+        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +tail(%d)", m->tail_n);
+    if (ksplit > 1 && !kcount)
+        return ltmi::dense_reduce_partials(m, ksplit, call.n_frames, (float *)call.out, call.ld_out, call.accumulate,
+                                           call.stream);
+    return LTMI_OK;
+}
+
 // generalised LDS-DMA kernel (k_dense_lds): any pixel width, 1 / 2 / 4 column groups per wave
 template <typename T, int NG, int TILES>
-static int launch_lds_ng_t(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                           int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch_lds_ng_t(ltmi_masks *m, const MaskCall &call) {
     using CFG = LdsCfg<NG, 0, TILES>;
     const int abl = m->tune_ksplit_ring == 31 ? 2 : (m->tune_ksplit_ring == 32 ? 1 : 0);
-    void (*kern)(const T *, int64_t, int64_t, int64_t, const float *, int, float *, int64_t, int,
-                 int, float *, int, const int32_t *, const float *const *, int *, const float *,
-                 const float *, const int32_t *, const int32_t *, int) =
-        abl == 2 ? lds_kernel<T, NG, 2, 0, 0, TILES>()
-                 : (abl == 1 ? lds_kernel<T, NG, 1, 0, 0, TILES>()
-                             : lds_kernel<T, NG, 0, 0, 0, TILES>());
-    const int32_t *rows = m->roi_rows;                  // ltmi_apply_masks_rows: frames through a row list
+    LdsKernel<T> kern = abl == 2 ? lds_kernel<T, NG, 2, 0, 0, TILES>()
+                                 : (abl == 1 ? lds_kernel<T, NG, 1, 0, 0, TILES>()
+                                             : lds_kernel<T, NG, 0, 0, 0, TILES>());
+    const int32_t *rows = call.rows;                    // ltmi_apply_masks_rows: frames through a row list
     if (rows) kern = lds_kernel<T, NG, 0, 2, 0, TILES>();
     // 1- / 2-byte integer pixels: exact float16 products (X16; tuning code 37 keeps the float32
     // instruction: tests, benches)
@@ -1886,74 +1923,35 @@ static int launch_lds_ng_t(ltmi_masks *m, const T *tile, int64_t n_frames, int64
         if (x16)
             kern = rows ? lds_kernel<T, NG, 0, 2, 0, TILES, true>()
                         : lds_kernel<T, NG, 0, 0, 0, TILES, true>();
-        m->x16_used = x16;
     }
     if (!kern)
         LTMI_FAIL(LTMI_E_DTYPE, "k_dense_lds<%s, NG=%d>: tuning code %d (ablations / one tile per wave) is built for "
                   "uint16 tiles and one column group only", typeid(T).name(), NG, m->tune_ksplit_ring);
     static bool attr_set[16][8] = {{false}};
     const int variant = (rows ? 3 : abl) + (x16 ? 4 : 0);
-    if (!attr_set[m->device & 15][variant]) {
-        LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     CFG::LDS_BYTES));
-        attr_set[m->device & 15][variant] = true;
-    }
     const float *img = x16 ? (NG == 1 ? m->img_h : m->img2_h) : (NG == 1 ? m->img : m->img2);
-    const int n_slots = NG == 1 ? m->n_chunks : m->n_slots2;
-    const int64_t gx = (n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
-    const int64_t gz = m->n_groups / NG;
-    int ksplit = m->tune_ksplit;
-    if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, n_slots);
-    ksplit = std::max(1, std::min(ksplit, n_slots));
-    {
-        const int per = (n_slots + ksplit - 1) / ksplit;
-        ksplit = (n_slots + per - 1) / per;
-    }
-    if (ksplit > 1) {
-        int rc = ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), stream);
-        if (rc != LTMI_OK) return rc;
-    }
-    dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
-    int *kcount = ksplit > 1 ? partial_counters(m, gx * gz) : nullptr;
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, stream, tile, ld, n_frames,
-                       m->n_px, img, n_slots, out, ld_out, m->n_cols, accumulate, partial_sums(m),
-                       ksplit_order(ksplit), rows, (const float *const *)nullptr, kcount,
-                       x16 ? (const float *)m->inv_scale : (const float *)nullptr,
-                       (const float *)m->tail_val, (const int32_t *)m->tail_col, (const int32_t *)m->tail_px,
-                       x16 ? m->tail_n : 0);
-    LTMI_HIP(hipGetLastError());
-    snprintf(m->last_kernel, sizeof(m->last_kernel),
-             "k_dense_lds<%s,NG=%d,ring=%d,tiles=%d%s%s> grid=(%u,%u,%u)", typeid(T).name(), NG,
-             CFG::RING, TILES, x16 ? ",f16" : "",
-             rows ? ",rows" : (abl ? (abl == 2 ? ",noDMA" : ",noMFMA") : ""), grid.x, grid.y, grid.z);
-    if (ksplit > 1 && !kcount) {
-        const int64_t n = n_frames * m->n_cols;
-        hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, (const float *)partial_sums(m), ksplit, n_frames, m->n_cols, out,
-                           ld_out, accumulate);
-        LTMI_HIP(hipGetLastError());
-    }
-    return LTMI_OK;
+    char name[96];
+    snprintf(name, sizeof(name), "k_dense_lds<%s,NG=%d,ring=%d,tiles=%d%s%s>", typeid(T).name(), NG, CFG::RING,
+             TILES, x16 ? ",f16" : "", rows ? ",rows" : (abl ? (abl == 2 ? ",noDMA" : ",noMFMA") : ""));
+    return launch_lds_kernel<T, CFG>(m, call, kern, img, NG == 1 ? m->n_chunks : m->n_slots2, m->n_groups / NG, x16,
+                                     &attr_set[m->device & 15][variant], name);
 }
 
 template <typename T, int NG>
-static int launch_lds_ng(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                         int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch_lds_ng(ltmi_masks *m, const MaskCall &call) {
     if constexpr (std::is_same<T, uint16_t>::value && NG == 1) {
-        if (lds_tiles(m) != 2 && !m->roi_rows)
-            return launch_lds_ng_t<T, NG, 1>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+        if (lds_tiles(m) != 2 && !call.rows) return launch_lds_ng_t<T, NG, 1>(m, call);
     }
-    return launch_lds_ng_t<T, NG, 2>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+    return launch_lds_ng_t<T, NG, 2>(m, call);
 }
 
-// NG MFMA groups + NE VALU columns (stacks of 16 NG + 1..4 columns)
-template <typename T, int NG, int NE, int TILES>
-static int launch_lds_extras_t(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                               int64_t ld_out, int accumulate, hipStream_t stream) {
+// NG MFMA groups + NE VALU columns (stacks of 16 NG + 1..4 columns), two frame tiles per wave
+template <typename T, int NG, int NE>
+static int launch_lds_extras(ltmi_masks *m, const MaskCall &call) {
+    constexpr int TILES = 2;
     using CFG = LdsCfg<NG, NE, TILES>;
-    auto kern = lds_kernel<T, NG, 0, 0, NE, TILES>();
-    const int32_t *rows = m->roi_rows;
-    if (rows) kern = lds_kernel<T, NG, 0, 2, NE, TILES>();
+    const int32_t *rows = call.rows;
+    LdsKernel<T> kern = rows ? lds_kernel<T, NG, 0, 2, NE, TILES>() : lds_kernel<T, NG, 0, 0, NE, TILES>();
     bool x16 = false;
     if constexpr (NE == 0 && NG >= 1 && sizeof(T) <= 2 && std::is_integral<T>::value) {
         // (exactly 3 groups: the float16 image of image 3, see launch_lds_ng_t)
@@ -1961,63 +1959,21 @@ static int launch_lds_extras_t(ltmi_masks *m, const T *tile, int64_t n_frames, i
         if (x16)
             kern = rows ? lds_kernel<T, NG, 0, 2, NE, TILES, true>()
                         : lds_kernel<T, NG, 0, 0, NE, TILES, true>();
-        m->x16_used = x16;
     }
     if (!kern)
         LTMI_FAIL(LTMI_E_DTYPE, "k_dense_lds<%s, NG=%d + %d VALU columns>: variant not built (tuning code %d)",
                   typeid(T).name(), NG, NE, m->tune_ksplit_ring);
     static bool attr_set[16][4] = {{false}};
     const int variant = (rows ? 1 : 0) + (x16 ? 2 : 0);
-    if (!attr_set[m->device & 15][variant]) {
-        LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     CFG::LDS_BYTES));
-        attr_set[m->device & 15][variant] = true;
-    }
-    const int n_slots = m->n_slots3;
-    const int64_t gx = (n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
-    int ksplit = m->tune_ksplit;
-    if (ksplit <= 0) ksplit = choose_ksplit(gx, n_slots);
-    ksplit = std::max(1, std::min(ksplit, n_slots));
-    {
-        const int per = (n_slots + ksplit - 1) / ksplit;
-        ksplit = (n_slots + per - 1) / per;
-    }
-    if (ksplit > 1) {
-        int rc = ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), stream);
-        if (rc != LTMI_OK) return rc;
-    }
-    dim3 grid((unsigned)gx, (unsigned)ksplit, 1);
-    int *kcount = ksplit > 1 ? partial_counters(m, gx) : nullptr;
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, stream, tile, ld, n_frames,
-                       m->n_px, x16 ? (const float *)m->img3_h : (const float *)m->img3, n_slots, out,
-                       ld_out, m->n_cols, accumulate, partial_sums(m), ksplit_order(ksplit), rows,
-                       (const float *const *)nullptr, kcount,
-                       x16 ? (const float *)m->inv_scale : (const float *)nullptr,
-                       (const float *)m->tail_val, (const int32_t *)m->tail_col, (const int32_t *)m->tail_px,
-                       x16 ? m->tail_n : 0);
-    LTMI_HIP(hipGetLastError());
+    char name[96];
     if (NE > 0)
-        snprintf(m->last_kernel, sizeof(m->last_kernel),
-                 "k_dense_lds<%s,NG=%d+%d VALU columns,ring=%d,tiles=%d%s> grid=(%u,%u,1)",
-                 typeid(T).name(), NG, NE, CFG::RING, TILES, rows ? ",rows" : "", grid.x, grid.y);
+        snprintf(name, sizeof(name), "k_dense_lds<%s,NG=%d+%d VALU columns,ring=%d,tiles=%d%s>", typeid(T).name(),
+                 NG, NE, CFG::RING, TILES, rows ? ",rows" : "");
     else
-        snprintf(m->last_kernel, sizeof(m->last_kernel),
-                 "k_dense_lds<%s,NG=%d,ring=%d,tiles=%d%s%s> grid=(%u,%u,1)", typeid(T).name(), NG,
-                 CFG::RING, TILES, x16 ? ",f16" : "", rows ? ",rows" : "", grid.x, grid.y);
-    if (ksplit > 1 && !kcount) {
-        const int64_t n = n_frames * m->n_cols;
-        hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, (const float *)partial_sums(m), ksplit, n_frames, m->n_cols, out,
-                           ld_out, accumulate);
-        LTMI_HIP(hipGetLastError());
-    }
-    return LTMI_OK;
-}
-
-template <typename T, int NG, int NE>
-static int launch_lds_extras(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                             int64_t ld_out, int accumulate, hipStream_t stream) {
-    return launch_lds_extras_t<T, NG, NE, 2>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+        snprintf(name, sizeof(name), "k_dense_lds<%s,NG=%d,ring=%d,tiles=%d%s%s>", typeid(T).name(), NG, CFG::RING,
+                 TILES, x16 ? ",f16" : "", rows ? ",rows" : "");
+    return launch_lds_kernel<T, CFG>(m, call, kern, x16 ? (const float *)m->img3_h : (const float *)m->img3,
+                                     m->n_slots3, 1, x16, &attr_set[m->device & 15][variant], name);
 }
 
 // (for the kernels of other translation units that split the pixel axis: ltmi_fold.hip)
@@ -2039,21 +1995,18 @@ static bool lds_kernel_applies(const ltmi_masks *m) {
 }
 
 template <typename T>
-static int launch_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                      int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch_lds(ltmi_masks *m, const MaskCall &call) {
     // float32 frames of a stack whose columns are even / odd under a mirror of the detector rows: half the pixels
     // on the matrix cores (ltmi_fold.hip; the handle knows the frame shape through ltmi_masks_set_sig_shape)
     if constexpr (std::is_same<T, float>::value) {
-        if (fold_takes(m, tile, ld))
-            return launch_fold(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+        if (fold_takes(m, (const float *)call.tile, call.ld_tile)) return launch_fold(m, call);
     }
     // ... and 2-byte integer frames of such a stack when it keeps the float32 matrix instruction (no float16
     // images: more small weights than their float32 tail takes -- radial-Fourier stacks) or is told to
     if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value) {
         const bool x16 = (m->img_h || m->img2_h || m->img3_h) && !f32_instruction_only(m);
-        if (!x16 && m->fold && fold_takes16(m, tile, ld, (int)sizeof(T)))
-            return launch_fold16(m, tile, (int)sizeof(T), std::is_signed<T>::value, n_frames, ld, out, ld_out,
-                                 accumulate, stream);
+        if (!x16 && m->fold && fold_takes16(m, call.tile, call.ld_tile, (int)sizeof(T)))
+            return launch_fold16(m, call, (int)sizeof(T), std::is_signed<T>::value);
     }
     if (m->ng == 1) {
         // at most 4 columns (CoM: 3, single-mask analyses: 1 or 2): all of them on the VALU -- a
@@ -2065,13 +2018,10 @@ static int launch_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld
         if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value)
             x16_group = m->img_h != nullptr && !f32_instruction_only(m);
         if (m->img3 && m->ng3 == 0 && m->tune_ksplit_ring != 33 && !x16_group) {
-            if (m->ne3 == 2)
-                return launch_lds_extras<T, 0, 2>(m, tile, n_frames, ld, out, ld_out, accumulate,
-                                                  stream);
-            return launch_lds_extras<T, 0, 4>(m, tile, n_frames, ld, out, ld_out, accumulate,
-                                              stream);
+            if (m->ne3 == 2) return launch_lds_extras<T, 0, 2>(m, call);
+            return launch_lds_extras<T, 0, 4>(m, call);
         }
-        return launch_lds_ng<T, 1>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+        return launch_lds_ng<T, 1>(m, call);
     }
     // 1- / 2-byte integer pixels: the VALU columns need float32 pixels, and with the exact float16
     // products (X16) a padded group costs less than they do -- the padded-group kernel instead
@@ -2079,9 +2029,8 @@ static int launch_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld
     if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value)
         x16_padded = m->ne3 > 0 && m->img2_h != nullptr && !f32_instruction_only(m);
     if (m->img3 && m->ng3 > 0 && m->tune_ksplit_ring != 33 && !x16_padded) {   // 33: force the padded-group kernel (bench)
-#define LTMI_EXTRAS(NG_, NE_)                                                                     \
-    if (m->ng3 == NG_ && m->ne3 == NE_)                                                           \
-        return launch_lds_extras<T, NG_, NE_>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+#define LTMI_EXTRAS(NG_, NE_) \
+    if (m->ng3 == NG_ && m->ne3 == NE_) return launch_lds_extras<T, NG_, NE_>(m, call);
         LTMI_EXTRAS(1, 2)
         LTMI_EXTRAS(2, 2)
         LTMI_EXTRAS(2, 4)
@@ -2090,9 +2039,8 @@ static int launch_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld
         LTMI_EXTRAS(3, 4)
 #undef LTMI_EXTRAS
     }
-    if (m->ng == 2)
-        return launch_lds_ng<T, 2>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-    return launch_lds_ng<T, 4>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+    if (m->ng == 2) return launch_lds_ng<T, 2>(m, call);
+    return launch_lds_ng<T, 4>(m, call);
 }
 
 // ---- shifted masks through the MFMA kernel -----------------------------------------------------------
@@ -2152,10 +2100,10 @@ static void shift_cache_destroy(ltmi_masks *m) {
 }
 
 template <typename T>
-static int launch_lds_shifted(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, int sig_h,
-                              int sig_w, const int32_t *shifts_host, float *out, int64_t ld_out,
-                              int accumulate, hipStream_t stream, bool *handled) {
+static int launch_lds_shifted(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, const int32_t *shifts_host,
+                              bool *handled) {
     *handled = false;
+    hipStream_t stream = call.stream;
     using CFG = LdsCfg<1, 0, 2>;
     ShiftCache *c = (ShiftCache *)m->shift_cache;
     if (!c) {
@@ -2180,7 +2128,7 @@ static int launch_lds_shifted(ltmi_masks *m, const T *tile, int64_t n_frames, in
     std::unordered_map<uint64_t, int> group_of;
     std::vector<uint64_t> keys;
     std::vector<std::vector<int32_t>> members;
-    for (int64_t f = 0; f < n_frames; ++f) {
+    for (int64_t f = 0; f < call.n_frames; ++f) {
         const uint64_t key = shift_key(shifts_host, f);
         auto it = group_of.find(key);
         int g;
@@ -2276,9 +2224,10 @@ static int launch_lds_shifted(ltmi_masks *m, const T *tile, int64_t n_frames, in
     }
     for (int gi = 0; gi < n_col_groups; ++gi)
         hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(CFG::WAVES * 64), CFG::LDS_BYTES, stream,
-                           tile, ld, n_frames, m->n_px, (const float *)nullptr, m->n_chunks,
-                           out + gi * GROUP, ld_out, std::min(GROUP, m->n_cols - gi * GROUP),
-                           accumulate, (float *)nullptr, 1, (const int32_t *)c->rows_dev,
+                           (const T *)call.tile, call.ld_tile, call.n_frames, m->n_px, (const float *)nullptr,
+                           m->n_chunks, (float *)call.out + gi * GROUP, call.ld_out,
+                           std::min(GROUP, m->n_cols - gi * GROUP), call.accumulate, (float *)nullptr, 1,
+                           (const int32_t *)c->rows_dev,
                            (const float *const *)c->wg_img_dev + (size_t)gi * n_wg, (int *)nullptr,
                            x16 ? (const float *)m->inv_scale + gi * GROUP : (const float *)nullptr,
                            (const float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, 0);
@@ -2291,8 +2240,9 @@ static int launch_lds_shifted(ltmi_masks *m, const T *tile, int64_t n_frames, in
 }
 
 template <typename T>
-static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                       int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch_mfma(ltmi_masks *m, const MaskCall &call) {
+    const void *tile = call.tile;
+    const int64_t n_frames = call.n_frames, ld = call.ld_tile;
     const bool aligned = (((uintptr_t)tile) % 16 == 0) && ((ld * (int64_t)sizeof(T)) % 16 == 0);
     // The LDS-DMA kernel does not need 16-B aligned rows: gfx950 serves global_load_lds_dwordx4 from
     // any element-aligned address (detectors with odd row lengths -- 515 x 515 uint16 -- run at the
@@ -2302,7 +2252,7 @@ static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t l
         // opt-in (LTMI_SPLIT=1 or tuning code 36): float32 frames against two or more column groups
         // as bf16 pieces on the bf16 matrix cores (ltmi_split.hip; measured slower than k_dense_lds
         // on C5, profiles/r03_split.txt, hence not the default).  The image is made on first use.
-        if (ltmi::split_selected(m->tune_ksplit_ring == 36) && m->blocks.empty() && !m->roi_rows &&
+        if (ltmi::split_selected(m->tune_ksplit_ring == 36) && m->blocks.empty() && !call.rows &&
             m->result_dtype != LTMI_F64 && ltmi::split_wanted(m->n_cols, m->n_px) &&
             vector_loads_ok(tile, ld, sizeof(T)) && m->tune_mt == 0 && m->tune_waves == 0 &&
             (m->tune_ksplit_ring == 0 || m->tune_ksplit_ring == 36)) {
@@ -2312,19 +2262,12 @@ static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t l
                                                    m->n_px, m->n_cols, &m->split);
                 if (rcs != LTMI_OK) return rcs;
             }
-            return ltmi::split_apply(m, m->split, tile, n_frames, ld, out, ld_out, accumulate, stream);
+            return ltmi::split_apply(m, m->split, call);
         }
     }
     if (vector_loads_ok(tile, ld, sizeof(T)) && m->tune_mt == 0 && m->tune_waves == 0 &&
-        lds_kernel_applies<T>(m)) {
-        m->x16_used = false;
-        const int rc_lds = launch_lds<T>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        if (rc_lds == LTMI_OK && m->x16_used && m->tail_n > 0) {
-            const size_t l = strlen(m->last_kernel);
-            snprintf(m->last_kernel + l, sizeof(m->last_kernel) - l, " +tail(%d)", m->tail_n);
-        }
-        return rc_lds;
-    }
+        lds_kernel_applies<T>(m))
+        return launch_lds<T>(m, call);
     int waves = m->tune_waves ? m->tune_waves : 4;
     int mt = m->tune_mt ? m->tune_mt : (n_frames >= 256 * waves * 32 ? 2 : 1);
     if (m->ng == 4) { mt = 1; }   // keep the accumulator/LDS budget in check
@@ -2340,22 +2283,15 @@ static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t l
             ksplit = (int)std::min<int64_t>((1024 + wgs - 1) / wgs, std::max(1, m->n_chunks / 8));
         }
     }
-    ksplit = std::max(1, std::min(ksplit, m->n_chunks));
-    // every split must own at least one chunk
-    {
-        const int per = (m->n_chunks + ksplit - 1) / ksplit;
-        ksplit = (m->n_chunks + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks)), m->n_chunks);
     if (ksplit > 1) {
-        int rc0 = ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), stream);
+        int rc0 = ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), call.stream);
         if (rc0 != LTMI_OK) return rc0;
     }
     int rc;
-#define LTMI_VARIANT(MT_, NG_, W_)                                                                \
-    (aligned ? launch_mfma_variant<T, MT_, NG_, W_, true>(m, tile, n_frames, ld, out, ld_out,      \
-                                                          accumulate, ksplit, stream)              \
-             : launch_mfma_variant<T, MT_, NG_, W_, false>(m, tile, n_frames, ld, out, ld_out,     \
-                                                           accumulate, ksplit, stream))
+#define LTMI_VARIANT(MT_, NG_, W_)                                             \
+    (aligned ? launch_mfma_variant<T, MT_, NG_, W_, true>(m, call, ksplit)      \
+             : launch_mfma_variant<T, MT_, NG_, W_, false>(m, call, ksplit))
     // (8-wave workgroups are a tuning choice only -- ltmi_masks_set_tuning(.., waves = 8, ..) -- and
     // compiled for uint16 pixels, the type the comparisons were made on; default: 4 waves)
     constexpr bool W8 = std::is_same<T, uint16_t>::value;
@@ -2376,45 +2312,39 @@ static int launch_mfma(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t l
     }
 #undef LTMI_VARIANT
     if (rc != LTMI_OK) return rc;
-    if (ksplit > 1) {
-        const int64_t n = n_frames * m->n_cols;
-        hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, (const float *)partial_sums(m), ksplit, n_frames, m->n_cols, out,
-                           ld_out, accumulate);
-        LTMI_HIP(hipGetLastError());
-    }
+    if (ksplit > 1)
+        return ltmi::dense_reduce_partials(m, ksplit, n_frames, (float *)call.out, call.ld_out, call.accumulate,
+                                           call.stream);
     return LTMI_OK;
 }
 
 // ---- generic launch ------------------------------------------------------------------------------
-// set by ltmi_apply_masks_shifted around the generic dispatch (per thread)
+// the shifted product of ltmi_apply_masks_shifted: an argument of the generic dispatch (null: the plain product)
 struct ShiftCtx {
     const int32_t *shifts = nullptr;
     int sig_h = 0, sig_w = 0;
     const int32_t *sel = nullptr;       // the guard's redo: the listed frames only (k_dense_shifted)
     const int *n_sel = nullptr;
 };
-static thread_local ShiftCtx g_shift;
 
 template <typename TIn, typename A, typename S>
-static int launch_generic(ltmi_masks *m, const void *tile, int64_t n_frames, int64_t ld, void *out,
-                          int64_t ld_out, int accumulate, hipStream_t stream) {
-    dim3 grid((unsigned)n_frames, (unsigned)((m->n_masks + GEN_MASKS - 1) / GEN_MASKS));
-    if (g_shift.shifts) {
-        if (g_shift.sel) grid.x = (unsigned)std::min<int64_t>(n_frames, 1024);   // (the list is short or empty)
-        hipLaunchKernelGGL((k_dense_shifted<TIn, A, S>), grid, dim3(256), 0, stream,
-                           (const TIn *)tile, ld, g_shift.sig_h, g_shift.sig_w, g_shift.shifts,
-                           (const A *)m->gmasks, (int)m->n_masks, (S *)out, ld_out, accumulate, g_shift.sel,
-                           g_shift.n_sel);
+static int launch_generic(ltmi_masks *m, const MaskCall &call, const ShiftCtx *shift) {
+    dim3 grid((unsigned)call.n_frames, (unsigned)((m->n_masks + GEN_MASKS - 1) / GEN_MASKS));
+    if (shift) {
+        if (shift->sel) grid.x = (unsigned)std::min<int64_t>(call.n_frames, 1024);   // (the list is short or empty)
+        hipLaunchKernelGGL((k_dense_shifted<TIn, A, S>), grid, dim3(256), 0, call.stream,
+                           (const TIn *)call.tile, call.ld_tile, shift->sig_h, shift->sig_w, shift->shifts,
+                           (const A *)m->gmasks, (int)m->n_masks, (S *)call.out, call.ld_out, call.accumulate,
+                           shift->sel, shift->n_sel);
         LTMI_HIP(hipGetLastError());
-        if (g_shift.sel) return LTMI_OK;                  // (the route's name stays that of the product)
+        if (shift->sel) return LTMI_OK;                   // (the route's name stays that of the product)
         snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_shifted<%s,%s> grid=(%u,%u)",
                  typeid(TIn).name(), typeid(A).name(), grid.x, grid.y);
         return LTMI_OK;
     }
-    hipLaunchKernelGGL((k_dense_generic<TIn, A, S>), grid, dim3(256), 0, stream, (const TIn *)tile,
-                       ld, n_frames, m->n_px, (const A *)m->gmasks, (int)m->n_masks, (S *)out,
-                       ld_out, accumulate);
+    hipLaunchKernelGGL((k_dense_generic<TIn, A, S>), grid, dim3(256), 0, call.stream, (const TIn *)call.tile,
+                       call.ld_tile, call.n_frames, m->n_px, (const A *)m->gmasks, (int)m->n_masks, (S *)call.out,
+                       call.ld_out, call.accumulate);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_generic<%s,%s> grid=(%u,%u)",
              typeid(TIn).name(), typeid(A).name(), grid.x, grid.y);
@@ -2422,60 +2352,65 @@ static int launch_generic(ltmi_masks *m, const void *tile, int64_t n_frames, int
 }
 
 template <typename A, typename S>
-static int dispatch_generic_real_in(ltmi_masks *m, const void *tile, int tile_dtype,
-                                    int64_t n_frames, int64_t ld, void *out, int64_t ld_out,
-                                    int accumulate, hipStream_t stream) {
-    switch (tile_dtype) {
+static int dispatch_generic_real_in(ltmi_masks *m, const MaskCall &call, const ShiftCtx *shift) {
+    switch (call.tile_dtype) {
         case LTMI_BOOL:
-        case LTMI_U8: return launch_generic<uint8_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_I8: return launch_generic<int8_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_U16: return launch_generic<uint16_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_I16: return launch_generic<int16_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_U32: return launch_generic<uint32_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_I32: return launch_generic<int32_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_U64: return launch_generic<uint64_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_I64: return launch_generic<int64_t, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_F32: return launch_generic<float, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_F64: return launch_generic<double, A, S>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+        case LTMI_U8: return launch_generic<uint8_t, A, S>(m, call, shift);
+        case LTMI_I8: return launch_generic<int8_t, A, S>(m, call, shift);
+        case LTMI_U16: return launch_generic<uint16_t, A, S>(m, call, shift);
+        case LTMI_I16: return launch_generic<int16_t, A, S>(m, call, shift);
+        case LTMI_U32: return launch_generic<uint32_t, A, S>(m, call, shift);
+        case LTMI_I32: return launch_generic<int32_t, A, S>(m, call, shift);
+        case LTMI_U64: return launch_generic<uint64_t, A, S>(m, call, shift);
+        case LTMI_I64: return launch_generic<int64_t, A, S>(m, call, shift);
+        case LTMI_F32: return launch_generic<float, A, S>(m, call, shift);
+        case LTMI_F64: return launch_generic<double, A, S>(m, call, shift);
     }
     LTMI_FAIL(LTMI_E_DTYPE, "tile dtype %s cannot be combined with result dtype %s",
-              dtype_name(tile_dtype), dtype_name(m->result_dtype));
+              dtype_name(call.tile_dtype), dtype_name(m->result_dtype));
 }
 
 template <typename A, typename S>
-static int dispatch_generic_int(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
-                                int64_t ld, void *out, int64_t ld_out, int accumulate,
-                                hipStream_t stream) {
-    if (tile_dtype > LTMI_I64)
+static int dispatch_generic_int(ltmi_masks *m, const MaskCall &call, const ShiftCtx *shift) {
+    if (call.tile_dtype > LTMI_I64)
         LTMI_FAIL(LTMI_E_DTYPE, "float/complex tile (%s) with integer result dtype %s",
-                  dtype_name(tile_dtype), dtype_name(m->result_dtype));
-    return dispatch_generic_real_in<A, S>(m, tile, tile_dtype, n_frames, ld, out, ld_out,
-                                          accumulate, stream);
+                  dtype_name(call.tile_dtype), dtype_name(m->result_dtype));
+    return dispatch_generic_real_in<A, S>(m, call, shift);
 }
 
-static int apply_generic(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
-                         int64_t ld, void *out, int64_t ld_out, int accumulate, hipStream_t stream) {
+static int apply_generic(ltmi_masks *m, const MaskCall &call, const ShiftCtx *shift) {
+    const int tile_dtype = call.tile_dtype;
     switch (m->result_dtype) {
-        case LTMI_F32: return dispatch_generic_real_in<float, float>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
-        case LTMI_F64: return dispatch_generic_real_in<double, double>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+        case LTMI_F32: return dispatch_generic_real_in<float, float>(m, call, shift);
+        case LTMI_F64: return dispatch_generic_real_in<double, double>(m, call, shift);
         case LTMI_C64:
-            if (tile_dtype == LTMI_C64) return launch_generic<cfloat, cfloat, cfloat>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+            if (tile_dtype == LTMI_C64) return launch_generic<cfloat, cfloat, cfloat>(m, call, shift);
             if (tile_dtype == LTMI_C128) LTMI_FAIL(LTMI_E_DTYPE, "complex128 tile with complex64 result");
-            return dispatch_generic_real_in<cfloat, cfloat>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            return dispatch_generic_real_in<cfloat, cfloat>(m, call, shift);
         case LTMI_C128:
-            if (tile_dtype == LTMI_C64) return launch_generic<cfloat, cdouble, cdouble>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-            if (tile_dtype == LTMI_C128) return launch_generic<cdouble, cdouble, cdouble>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-            return dispatch_generic_real_in<cdouble, cdouble>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            if (tile_dtype == LTMI_C64) return launch_generic<cfloat, cdouble, cdouble>(m, call, shift);
+            if (tile_dtype == LTMI_C128) return launch_generic<cdouble, cdouble, cdouble>(m, call, shift);
+            return dispatch_generic_real_in<cdouble, cdouble>(m, call, shift);
         case LTMI_BOOL: case LTMI_U8: case LTMI_I8:
-            return dispatch_generic_int<uint64_t, uint8_t>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            return dispatch_generic_int<uint64_t, uint8_t>(m, call, shift);
         case LTMI_U16: case LTMI_I16:
-            return dispatch_generic_int<uint64_t, uint16_t>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            return dispatch_generic_int<uint64_t, uint16_t>(m, call, shift);
         case LTMI_U32: case LTMI_I32:
-            return dispatch_generic_int<uint64_t, uint32_t>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            return dispatch_generic_int<uint64_t, uint32_t>(m, call, shift);
         case LTMI_U64: case LTMI_I64:
-            return dispatch_generic_int<uint64_t, uint64_t>(m, tile, tile_dtype, n_frames, ld, out, ld_out, accumulate, stream);
+            return dispatch_generic_int<uint64_t, uint64_t>(m, call, shift);
     }
     LTMI_FAIL(LTMI_E_DTYPE, "unsupported result dtype %d", m->result_dtype);
+}
+
+// the guard decision and the product: ltmi_apply_masks after its argument checks, and what a column block runs
+static int apply_masks_call(ltmi_masks *m, const MaskCall &call) {
+    // float frames against a stack whose fast kernels also multiply zeros the stack does not hold (or, for a dense
+    // stack held as column blocks, skip zeros it does hold): frames with non-finite results are computed again with
+    // the reference's arithmetic (ltmi_guard.hip)
+    if (ltmi::guard_wanted(m, call.tile_dtype)) return ltmi::guard_apply(m, call);
+    if (m->guard) ltmi::guard_note_unchecked(m);
+    return ltmi::apply_masks_unguarded(m, call);
 }
 
 extern "C" int ltmi_apply_masks(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
@@ -2493,36 +2428,22 @@ extern "C" int ltmi_apply_masks(ltmi_masks *m, const void *tile, int tile_dtype,
     // (a runtime call that failed OUTSIDE the library -- a refused host registration, say -- leaves its code as
     // the thread's sticky last error; the launch checks below must not report it for these kernels)
     (void)hipGetLastError();
-    hipStream_t stream = (hipStream_t)stream_;
     LTMI_HIP(hipSetDevice(m->device));
-    // float frames against a stack whose fast kernels also multiply zeros the stack does not hold (or, for a dense
-    // stack held as column blocks, skip zeros it does hold): frames with non-finite results are computed again with
-    // the reference's arithmetic (ltmi_guard.hip)
-    if (ltmi::guard_wanted(m, tile_dtype))
-        return ltmi::guard_apply(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate, stream);
-    if (m->guard) ltmi::guard_note_unchecked(m);
-    return ltmi::apply_masks_unguarded(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate, stream);
+    return apply_masks_call(m, MaskCall{tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate,
+                                        (hipStream_t)stream_});
 }
 
-int ltmi::apply_masks_unguarded(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
-                                void *out, int64_t ld_out, int accumulate, hipStream_t stream) {
-    void *stream_ = (void *)stream;
+int ltmi::apply_masks_unguarded(ltmi_masks *m, const MaskCall &call) {
+    const int tile_dtype = call.tile_dtype;
     m->last_exact = false;
-    if (m->kind == 2)
-        return ltmi::csr_apply(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate,
-                               stream);
+    if (m->kind == 2) return ltmi::csr_apply(m, call);
     if (m->kind == 0 && mfma_tile_dtype(tile_dtype) && !m->blocks.empty() &&
         m->tune_mt == 0 && m->tune_waves == 0 && m->tune_ksplit_ring != 33) {
         const size_t elem = (size_t)dtype_size(m->result_dtype);
         for (size_t b = 0; b < m->blocks.size(); ++b) {
-            ltmi_masks *c = m->blocks[b];
-            c->tune_ksplit = m->tune_ksplit;
-            c->tune_ksplit_ring = m->tune_ksplit_ring;
-            c->roi_rows = m->roi_rows;                      // (ltmi_apply_masks_rows: every block reads them)
-            const int rc = ltmi_apply_masks(c, tile, tile_dtype, n_frames, ld_tile,
-                                            (unsigned char *)out + (size_t)m->block_first[b] * elem,
-                                            ld_out, accumulate, stream_);
-            c->roi_rows = nullptr;
+            MaskCall block = call;
+            block.out = (unsigned char *)call.out + (size_t)m->block_first[b] * elem;
+            const int rc = apply_masks_call(m->blocks[b], block);
             if (rc != LTMI_OK) return rc;
         }
         snprintf(m->last_kernel, sizeof(m->last_kernel), "%zu column blocks, last: %.90s",
@@ -2530,26 +2451,25 @@ int ltmi::apply_masks_unguarded(ltmi_masks *m, const void *tile, int tile_dtype,
         return LTMI_OK;
     }
     if (m->kind == 0 && mfma_tile_dtype(tile_dtype)) {
-        float *o = (float *)out;
-        const int64_t ldo = ld_out * (m->result_dtype == LTMI_C64 ? 2 : 1);
+        MaskCall f32 = call;                                // (complex64 rows as 2 floats per mask)
+        f32.ld_out = call.ld_out * (m->result_dtype == LTMI_C64 ? 2 : 1);
         switch (tile_dtype) {
             case LTMI_BOOL:
-            case LTMI_U8: return launch_mfma<uint8_t>(m, (const uint8_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-            case LTMI_I8: return launch_mfma<int8_t>(m, (const int8_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-            case LTMI_U16: return launch_mfma<uint16_t>(m, (const uint16_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-            case LTMI_I16: return launch_mfma<int16_t>(m, (const int16_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-            case LTMI_F32: return launch_mfma<float>(m, (const float *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
+            case LTMI_U8: return launch_mfma<uint8_t>(m, f32);
+            case LTMI_I8: return launch_mfma<int8_t>(m, f32);
+            case LTMI_U16: return launch_mfma<uint16_t>(m, f32);
+            case LTMI_I16: return launch_mfma<int16_t>(m, f32);
+            case LTMI_F32: return launch_mfma<float>(m, f32);
         }
     }
     if (m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128 ||
         (m->result_dtype >= LTMI_U8 && m->result_dtype <= LTMI_I64)) {
         bool handled = false;
-        const int rc = ltmi::dense64_apply(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out,
-                                           accumulate, stream, &handled);
+        const int rc = ltmi::dense64_apply(m, m->img64, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
-    if (m->roi_rows) LTMI_FAIL(LTMI_E_INVALID, "ltmi_apply_masks: the generic kernel does not take a row list");
-    return apply_generic(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate, stream);
+    if (call.rows) LTMI_FAIL(LTMI_E_INVALID, "ltmi_apply_masks: the generic kernel does not take a row list");
+    return apply_generic(m, call, nullptr);
 }
 
 // Frames of a tile through a row list (a region of interest without a gathered copy):
@@ -2569,25 +2489,23 @@ extern "C" int ltmi_apply_masks_rows(ltmi_masks *m, const void *tile, int tile_d
         LTMI_FAIL(LTMI_E_DTYPE, "ltmi_apply_masks_rows: unknown tile dtype %d", tile_dtype);
     if (n_rows == 0) { *handled = 1; return LTMI_OK; }
     if (!tile || !out || !rows) LTMI_FAIL(LTMI_E_INVALID, "ltmi_apply_masks_rows: null pointer");
+    // the product of ltmi_apply_masks, frames read through the row list
+    auto product = [&]() -> int {
+        *handled = 1;
+        (void)hipGetLastError();                            // (see ltmi_apply_masks)
+        LTMI_HIP(hipSetDevice(m->device));
+        return apply_masks_call(m, MaskCall{tile, tile_dtype, n_rows, ld_tile, out, ld_out, accumulate,
+                                            (hipStream_t)stream_, rows});
+    };
     if (m->kind == 2) {
         // sparse stacks: the blocked image's kernel reads frames through the row list as well
         if (n_rows >= (1ll << 31) || !ltmi::csr_rows_ok(m, tile, tile_dtype, ld_tile)) return LTMI_OK;
-        m->roi_rows = rows;
-        const int rc = ltmi_apply_masks(m, tile, tile_dtype, n_rows, ld_tile, out, ld_out, accumulate,
-                                        stream_);
-        m->roi_rows = nullptr;
-        *handled = 1;
-        return rc;
+        return product();
     }
     if (m->kind != 2 && m->img64 && m->blocks.empty() && n_rows < (1ll << 31) &&
         ltmi::dense64_rows_ok(m, tile, tile_dtype, ld_tile)) {
         // float64 / complex128 results: the f64 LDS-DMA kernel reads frames through the row list
-        m->roi_rows = rows;
-        const int rc = ltmi_apply_masks(m, tile, tile_dtype, n_rows, ld_tile, out, ld_out, accumulate,
-                                        stream_);
-        m->roi_rows = nullptr;
-        *handled = 1;
-        return rc;
+        return product();
     }
     if (m->kind != 0 || !mfma_tile_dtype(tile_dtype) || m->tune_mt != 0 ||
         m->tune_waves != 0 || m->tune_ksplit_ring == 33 || n_rows >= (1ll << 31) ||
@@ -2605,12 +2523,7 @@ extern "C" int ltmi_apply_masks_rows(ltmi_masks *m, const void *tile, int tile_d
     bool lds = m->blocks.empty() ? lds_ok(m) : true;
     for (const ltmi_masks *b : m->blocks) lds = lds && lds_ok(b);
     if (!lds) return LTMI_OK;
-    m->roi_rows = rows;
-    const int rc = ltmi_apply_masks(m, tile, tile_dtype, n_rows, ld_tile, out, ld_out, accumulate,
-                                    stream_);
-    m->roi_rows = nullptr;
-    *handled = 1;
-    return rc;
+    return product();
 }
 
 // ---- shifted masks, float64 / complex128 / exact-integer results ---------------------------------------
@@ -2651,10 +2564,11 @@ static int ensure_bytes(void **buf, size_t *have, size_t need, hipStream_t strea
     return LTMI_OK;
 }
 
-static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
-                     int sig_h, int sig_w, const int32_t *shifts_host, void *out, int64_t ld_out,
-                     int accumulate, hipStream_t stream, bool *handled) {
+static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, const int32_t *shifts_host,
+                     bool *handled) {
     *handled = false;
+    hipStream_t stream = call.stream;
+    const int64_t n_frames = call.n_frames;
     ShiftCache *c = (ShiftCache *)m->shift_cache;
     if (!c) {
         c = new (std::nothrow) ShiftCache();
@@ -2709,17 +2623,9 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
                                                    (int)(int32_t)(key & 0xffffffffu), img, stream);
         if (rc != LTMI_OK) return rc;
     }
-    double *const img_plain = m->img64;
-    auto run = [&](double *img, const void *frames, int64_t n, int64_t ld, void *dst, int64_t ld_dst,
-                   int acc, bool *ok) {
-        m->img64 = img;
-        const int rc = ltmi::dense64_apply(m, frames, tile_dtype, n, ld, dst, ld_dst, acc, stream, ok);
-        m->img64 = img_plain;
-        return rc;
-    };
     if (keys.size() == 1) {                      // one shift for the whole tile: no gather, no scatter
         bool ok = false;
-        const int rc = run(c->images64[keys[0]], tile, n_frames, ld_tile, out, ld_out, accumulate, &ok);
+        const int rc = ltmi::dense64_apply(m, c->images64[keys[0]], call, &ok);
         if (rc != LTMI_OK) return rc;
         if (ok) {
             const size_t len = strlen(m->last_kernel);
@@ -2729,7 +2635,8 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
         return LTMI_OK;
     }
     // several shifts: frame numbers of all groups to the device, then group by group
-    const size_t esz = (size_t)dtype_size(tile_dtype), rsz = (size_t)dtype_size(m->result_dtype);
+    const int64_t ld_out = call.ld_out;
+    const size_t esz = (size_t)dtype_size(call.tile_dtype), rsz = (size_t)dtype_size(m->result_dtype);
     size_t largest = 0;
     c->stage = (c->stage + 1) % ShiftCache::STAGES;
     std::vector<int64_t> &idx_host = c->idx_stage[c->stage];
@@ -2758,11 +2665,12 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
         const int64_t n = (int64_t)members[g].size();
         const int64_t *idx = c->idx_dev + first;
         first += (size_t)n;
-        rc = ltmi_gather_rows(m->device, tile, ld_tile * (int64_t)esz, idx, n, m->n_px * (int64_t)esz,
+        rc = ltmi_gather_rows(m->device, call.tile, call.ld_tile * (int64_t)esz, idx, n, m->n_px * (int64_t)esz,
                               c->gather, stream);
         if (rc != LTMI_OK) return rc;
         bool ok = false;
-        rc = run(c->images64[keys[g]], c->gather, n, m->n_px, c->res, m->n_masks, 0, &ok);
+        rc = ltmi::dense64_apply(m, c->images64[keys[g]],
+                                 MaskCall{c->gather, call.tile_dtype, n, m->n_px, c->res, m->n_masks, 0, stream}, &ok);
         if (rc != LTMI_OK) return rc;
         if (!ok) {
             if (g == 0) return LTMI_OK;          // (nothing written yet: the per-frame kernel takes over)
@@ -2773,14 +2681,14 @@ static int shifted64(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_
         const int64_t ldo = ld_out * (m->result_dtype == LTMI_C128 ? 2 : 1);
         const dim3 grid((unsigned)((n * n_cols + 255) / 256));
         switch (m->result_dtype == LTMI_C128 ? 8 : (int)rsz) {
-            case 1: hipLaunchKernelGGL(k_scatter_rows<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t *)c->res, n, n_cols, idx, (uint8_t *)out, ldo, accumulate); break;
-            case 2: hipLaunchKernelGGL(k_scatter_rows<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t *)c->res, n, n_cols, idx, (uint16_t *)out, ldo, accumulate); break;
-            case 4: hipLaunchKernelGGL(k_scatter_rows<uint32_t>, grid, dim3(256), 0, stream, (const uint32_t *)c->res, n, n_cols, idx, (uint32_t *)out, ldo, accumulate); break;
+            case 1: hipLaunchKernelGGL(k_scatter_rows<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t *)c->res, n, n_cols, idx, (uint8_t *)call.out, ldo, call.accumulate); break;
+            case 2: hipLaunchKernelGGL(k_scatter_rows<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t *)c->res, n, n_cols, idx, (uint16_t *)call.out, ldo, call.accumulate); break;
+            case 4: hipLaunchKernelGGL(k_scatter_rows<uint32_t>, grid, dim3(256), 0, stream, (const uint32_t *)c->res, n, n_cols, idx, (uint32_t *)call.out, ldo, call.accumulate); break;
             default:
                 if (m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128)
-                    hipLaunchKernelGGL(k_scatter_rows<double>, grid, dim3(256), 0, stream, (const double *)c->res, n, n_cols, idx, (double *)out, ldo, accumulate);
+                    hipLaunchKernelGGL(k_scatter_rows<double>, grid, dim3(256), 0, stream, (const double *)c->res, n, n_cols, idx, (double *)call.out, ldo, call.accumulate);
                 else
-                    hipLaunchKernelGGL(k_scatter_rows<uint64_t>, grid, dim3(256), 0, stream, (const uint64_t *)c->res, n, n_cols, idx, (uint64_t *)out, ldo, accumulate);
+                    hipLaunchKernelGGL(k_scatter_rows<uint64_t>, grid, dim3(256), 0, stream, (const uint64_t *)c->res, n, n_cols, idx, (uint64_t *)call.out, ldo, call.accumulate);
                 break;
         }
         LTMI_HIP(hipGetLastError());
@@ -2838,13 +2746,9 @@ extern "C" int ltmi_apply_masks_shifted(ltmi_masks *m, const void *tile, int til
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_apply_masks_shifted: null pointer");
     LTMI_HIP(hipSetDevice(m->device));
     if (m->guard) ltmi::guard_note_unchecked(m);
-    g_shift.shifts = shifts;
-    g_shift.sig_h = sig_h;
-    g_shift.sig_w = sig_w;
-    const int rc = apply_generic(m, tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate,
-                                 (hipStream_t)stream_);
-    g_shift = ShiftCtx();
-    return rc;
+    const ShiftCtx shift{shifts, sig_h, sig_w};
+    return apply_generic(m, MaskCall{tile, tile_dtype, n_frames, ld_tile, out, ld_out, accumulate,
+                                     (hipStream_t)stream_}, &shift);
 }
 
 extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, int tile_dtype,
@@ -2895,13 +2799,8 @@ extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, in
         int32_t *listed = nullptr;
         rc = ltmi::guard_list_rows(m, target, ld_t, n_frames, stream, &n_listed, &listed);
         if (rc != LTMI_OK) return rc;
-        g_shift.shifts = shifts_dev;
-        g_shift.sig_h = sig_h;
-        g_shift.sig_w = sig_w;
-        g_shift.sel = listed;
-        g_shift.n_sel = n_listed;
-        rc = apply_generic(m, tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream);
-        g_shift = ShiftCtx();
+        const ShiftCtx redo{shifts_dev, sig_h, sig_w, listed, n_listed};
+        rc = apply_generic(m, MaskCall{tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream}, &redo);
         if (rc != LTMI_OK) return rc;
         const size_t len = strlen(m->last_kernel);
         snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
@@ -2910,14 +2809,15 @@ extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, in
     if (lds_route) {
         bool handled = false;
         int rc = LTMI_OK;
-        const int cw = (m->result_dtype == LTMI_C64) ? 2 : 1;
-        const int64_t ldo = cw * ld_out;
+        const int cw = (m->result_dtype == LTMI_C64) ? 2 : 1;   // (complex64 rows as 2 floats per mask)
+        // (integer frames are never checked: their target is `out`)
+        const MaskCall call{tile, tile_dtype, n_frames, ld_tile, target, cw * ld_t, acc_t, stream};
         switch (tile_dtype) {
-            case LTMI_U8: rc = launch_lds_shifted<uint8_t>(m, (const uint8_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
-            case LTMI_I8: rc = launch_lds_shifted<int8_t>(m, (const int8_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
-            case LTMI_U16: rc = launch_lds_shifted<uint16_t>(m, (const uint16_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
-            case LTMI_I16: rc = launch_lds_shifted<int16_t>(m, (const int16_t *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)out, ldo, accumulate, stream, &handled); break;
-            case LTMI_F32: rc = launch_lds_shifted<float>(m, (const float *)tile, n_frames, ld_tile, sig_h, sig_w, shifts_host, (float *)target, cw * ld_t, acc_t, stream, &handled); break;
+            case LTMI_U8: rc = launch_lds_shifted<uint8_t>(m, call, sig_h, sig_w, shifts_host, &handled); break;
+            case LTMI_I8: rc = launch_lds_shifted<int8_t>(m, call, sig_h, sig_w, shifts_host, &handled); break;
+            case LTMI_U16: rc = launch_lds_shifted<uint16_t>(m, call, sig_h, sig_w, shifts_host, &handled); break;
+            case LTMI_I16: rc = launch_lds_shifted<int16_t>(m, call, sig_h, sig_w, shifts_host, &handled); break;
+            case LTMI_F32: rc = launch_lds_shifted<float>(m, call, sig_h, sig_w, shifts_host, &handled); break;
             default: break;
         }
         if (rc != LTMI_OK) return rc;
@@ -2925,8 +2825,8 @@ extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, in
     }
     if (f64_route) {
         bool handled = false;
-        const int rc = shifted64(m, tile, tile_dtype, n_frames, ld_tile, sig_h, sig_w, shifts_host, target,
-                                 ld_t, acc_t, stream, &handled);
+        const int rc = shifted64(m, MaskCall{tile, tile_dtype, n_frames, ld_tile, target, ld_t, acc_t, stream},
+                                 sig_h, sig_w, shifts_host, &handled);
         if (rc != LTMI_OK) return rc;
         if (handled) return redo_and_deliver();
     }

@@ -568,8 +568,9 @@ static int ensure_ws64(ltmi_masks *m, size_t need, hipStream_t stream) {
 
 // at least one full mask chunk: the LDS-DMA kernel
 template <typename T>
-static int launch64_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, double *out,
-                        int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch64_lds(ltmi_masks *m, const double *img64, const MaskCall &call) {
+    const T *tile = (const T *)call.tile;
+    double *out = (double *)call.out;
     using CFG = Lds64Cfg;
     auto kern = k_dense_lds64<T>;
     static bool attr_set[16] = {false};
@@ -578,31 +579,27 @@ static int launch64_lds(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t 
                                      CFG::LDS_BYTES));
         attr_set[m->device & 15] = true;
     }
-    const int64_t gx = (n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
+    const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
     const int64_t gz = m->n_groups64;
     int ksplit = m->tune_ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, m->n_chunks64);
-    ksplit = std::max(1, std::min(ksplit, m->n_chunks64));
-    {
-        const int per = (m->n_chunks64 + ksplit - 1) / ksplit;
-        ksplit = (m->n_chunks64 + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks64)), m->n_chunks64);
     if (ksplit > 1) {
-        int rc = ensure_ws64(m, (size_t)ksplit * n_frames * n_cols64(m) * sizeof(double), stream);
+        int rc = ensure_ws64(m, (size_t)ksplit * call.n_frames * n_cols64(m) * sizeof(double), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, stream, tile, ld, n_frames,
-                       m->n_px, (const double *)m->img64, m->n_chunks64, out, ld_out,
-                       (int)n_cols64(m), accumulate, (double *)m->ws64, ksplit, m->roi_rows);
+    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, call.stream, tile, call.ld_tile,
+                       call.n_frames, m->n_px, img64, m->n_chunks64, out, call.ld_out, (int)n_cols64(m),
+                       call.accumulate, (double *)m->ws64, ksplit, call.rows);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_lds64<%s%s> grid=(%u,%u,%u)",
-             typeid(T).name(), m->roi_rows ? ",rows" : "", grid.x, grid.y, grid.z);
+             typeid(T).name(), call.rows ? ",rows" : "", grid.x, grid.y, grid.z);
     if (ksplit > 1) {
-        const int64_t n = n_frames * n_cols64(m);
+        const int64_t n = call.n_frames * n_cols64(m);
         hipLaunchKernelGGL(k_reduce_partials64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, (const double *)m->ws64, ksplit, n_frames, (int)n_cols64(m), out,
-                           ld_out, accumulate);
+                           call.stream, (const double *)m->ws64, ksplit, call.n_frames, (int)n_cols64(m), out,
+                           call.ld_out, call.accumulate);
         LTMI_HIP(hipGetLastError());
     }
     return LTMI_OK;
@@ -637,18 +634,17 @@ bool dense64_rows_ok(const ltmi_masks *m, const void *tile, int tile_dtype, int6
 }
 
 template <typename T>
-static int launch64(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, double *out,
-                    int64_t ld_out, int accumulate, hipStream_t stream) {
-    {
-        // tune_mt == 1 (ltmi_masks_set_tuning): force the direct-load kernel (bench comparison)
-        // (rows need not be 16-B aligned: LDS-DMA reads from any element-aligned address)
-        if (m->tune_mt != 1 && m->n_px >= KC64 && vector_loads_ok(tile, ld, sizeof(T)))
-            return launch64_lds<T>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
-    }
-    if (m->roi_rows) LTMI_FAIL(LTMI_E_INVALID, "k_dense_mfma_f64 does not take a row list");
+static int launch64(ltmi_masks *m, const double *img64, const MaskCall &call) {
+    const T *tile = (const T *)call.tile;
+    double *out = (double *)call.out;
+    // tune_mt == 1 (ltmi_masks_set_tuning): force the direct-load kernel (bench comparison)
+    // (rows need not be 16-B aligned: LDS-DMA reads from any element-aligned address)
+    if (m->tune_mt != 1 && m->n_px >= KC64 && vector_loads_ok(tile, call.ld_tile, sizeof(T)))
+        return launch64_lds<T>(m, img64, call);
+    if (call.rows) LTMI_FAIL(LTMI_E_INVALID, "k_dense_mfma_f64 does not take a row list");
     constexpr int WAVES = 4;
-    const bool vec = (((uintptr_t)tile) % (4 * sizeof(T)) == 0) && (ld % 4 == 0);
-    const int64_t gx = (n_frames + WAVES * 16 - 1) / (WAVES * 16);
+    const bool vec = (((uintptr_t)tile) % (4 * sizeof(T)) == 0) && (call.ld_tile % 4 == 0);
+    const int64_t gx = (call.n_frames + WAVES * 16 - 1) / (WAVES * 16);
     const int64_t gz = m->n_groups64;
     int ksplit = m->tune_ksplit;
     if (ksplit <= 0) {
@@ -657,16 +653,12 @@ static int launch64(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, 
             ksplit = (int)std::min<int64_t>((1024 + gx * gz - 1) / (gx * gz),
                                             std::max(1, m->n_chunks64 / 8));
     }
-    ksplit = std::max(1, std::min(ksplit, m->n_chunks64));
-    {
-        const int per = (m->n_chunks64 + ksplit - 1) / ksplit;
-        ksplit = (m->n_chunks64 + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks64)), m->n_chunks64);
     if (ksplit > 1) {
-        const size_t need = (size_t)ksplit * n_frames * n_cols64(m) * sizeof(double);
+        const size_t need = (size_t)ksplit * call.n_frames * n_cols64(m) * sizeof(double);
         if (m->ws64_bytes < need) {
             if (m->ws64) {
-                LTMI_HIP(hipStreamSynchronize(stream));
+                LTMI_HIP(hipStreamSynchronize(call.stream));
                 LTMI_HIP(hipFree(m->ws64));
                 m->ws64 = nullptr;
                 m->ws64_bytes = 0;
@@ -680,33 +672,36 @@ static int launch64(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, 
     LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, stream, tile, ld, n_frames, m->n_px,
-                       (const double *)m->img64, m->n_chunks64, out, ld_out, (int)n_cols64(m),
-                       accumulate, (double *)m->ws64, ksplit);
+    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
+                       img64, m->n_chunks64, out, call.ld_out, (int)n_cols64(m),
+                       call.accumulate, (double *)m->ws64, ksplit);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_mfma_f64<%s,%s> grid=(%u,%u,%u)",
              typeid(T).name(), vec ? "vec" : "guarded", grid.x, grid.y, grid.z);
     if (ksplit > 1) {
-        const int64_t n = n_frames * n_cols64(m);
+        const int64_t n = call.n_frames * n_cols64(m);
         hipLaunchKernelGGL(k_reduce_partials64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, (const double *)m->ws64, ksplit, n_frames, (int)n_cols64(m), out,
-                           ld_out, accumulate);
+                           call.stream, (const double *)m->ws64, ksplit, call.n_frames, (int)n_cols64(m), out,
+                           call.ld_out, call.accumulate);
         LTMI_HIP(hipGetLastError());
     }
     return LTMI_OK;
 }
 
 // -> LTMI_OK and *handled = true if the tile went through the f64 matrix kernel
-int dense64_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld,
-                  void *out, int64_t ld_out, int accumulate, hipStream_t stream, bool *handled) {
+int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool *handled) {
     *handled = false;
-    if (!m->img64) return LTMI_OK;
+    if (!img64) return LTMI_OK;
+    const int tile_dtype = call.tile_dtype, accumulate = call.accumulate;
+    const int64_t n_frames = call.n_frames, ld_out = call.ld_out;
+    void *out = call.out;
+    hipStream_t stream = call.stream;
     const bool int_result = m->result_dtype >= LTMI_U8 && m->result_dtype <= LTMI_I64;
     if (!int_result && m->result_dtype != LTMI_F64 && m->result_dtype != LTMI_C128) return LTMI_OK;
     // complex128 masks on REAL frames: 2 real f64 columns per mask, the result row is the interleaved
     // complex128 row (complex frames stay with the generic kernel: `default` below)
-    double *o = (double *)out;
-    int64_t ld_o = ld_out * m->cpm64;
+    MaskCall f64 = call;
+    f64.ld_out = ld_out * m->cpm64;
     if (int_result) {
         // Integer masks x integer frames (preferred_dtype / mask_dtype integer: NumPy integer matmul,
         // wrap-around).  If every possible partial sum fits 2^52 the f64 FMA chain is EXACT, so the
@@ -724,23 +719,23 @@ int dense64_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_fra
             LTMI_HIP(hipMalloc(&m->res64, need));
             m->res64_bytes = need;
         }
-        o = (double *)m->res64;
-        ld_o = m->n_masks;
+        f64.out = m->res64;
+        f64.ld_out = m->n_masks;
+        f64.accumulate = 0;
     }
-    const int acc64 = int_result ? 0 : accumulate;
     int rc;
     switch (tile_dtype) {
         case LTMI_BOOL:
-        case LTMI_U8: rc = launch64<uint8_t>(m, (const uint8_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_I8: rc = launch64<int8_t>(m, (const int8_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_U16: rc = launch64<uint16_t>(m, (const uint16_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_I16: rc = launch64<int16_t>(m, (const int16_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_U32: rc = launch64<uint32_t>(m, (const uint32_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_I32: rc = launch64<int32_t>(m, (const int32_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_U64: rc = launch64<uint64_t>(m, (const uint64_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_I64: rc = launch64<int64_t>(m, (const int64_t *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_F32: rc = launch64<float>(m, (const float *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
-        case LTMI_F64: rc = launch64<double>(m, (const double *)tile, n_frames, ld, o, ld_o, acc64, stream); break;
+        case LTMI_U8: rc = launch64<uint8_t>(m, img64, f64); break;
+        case LTMI_I8: rc = launch64<int8_t>(m, img64, f64); break;
+        case LTMI_U16: rc = launch64<uint16_t>(m, img64, f64); break;
+        case LTMI_I16: rc = launch64<int16_t>(m, img64, f64); break;
+        case LTMI_U32: rc = launch64<uint32_t>(m, img64, f64); break;
+        case LTMI_I32: rc = launch64<int32_t>(m, img64, f64); break;
+        case LTMI_U64: rc = launch64<uint64_t>(m, img64, f64); break;
+        case LTMI_I64: rc = launch64<int64_t>(m, img64, f64); break;
+        case LTMI_F32: rc = launch64<float>(m, img64, f64); break;
+        case LTMI_F64: rc = launch64<double>(m, img64, f64); break;
         default: return LTMI_OK;           // complex tiles: generic kernel
     }
     if (rc != LTMI_OK) return rc;

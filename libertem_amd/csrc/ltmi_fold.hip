@@ -1038,8 +1038,9 @@ bool ltmi::fold_takes(const ltmi_masks *m, const float *tile, int64_t ld) {
 }
 
 template <int NGE, int NGO>
-static int launch_fold_t(ltmi_masks *m, const float *tile, int64_t n_frames, int64_t ld, float *out, int64_t ld_out,
-                         int accumulate, hipStream_t stream) {
+static int launch_fold_t(ltmi_masks *m, const MaskCall &call) {
+    const float *tile = (const float *)call.tile;
+    float *out = (float *)call.out;
     const FoldImage *f = (const FoldImage *)m->fold;
     const int abl = m->tune_ksplit_ring == 31 ? 2 : (m->tune_ksplit_ring == 32 ? 1 : 0);
     auto kern = abl == 2 ? k_dense_fold<NGE, NGO, 2> : (abl == 1 ? k_dense_fold<NGE, NGO, 1> : k_dense_fold<NGE, NGO, 0>);
@@ -1049,16 +1050,12 @@ static int launch_fold_t(ltmi_masks *m, const float *tile, int64_t n_frames, int
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr_set[m->device & 15][abl] = true;
     }
-    const int64_t gx = (n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
+    const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
     int ksplit = m->tune_ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx, f->n_stages);
-    ksplit = std::max(1, std::min(ksplit, f->n_stages));
-    {
-        const int per = (f->n_stages + ksplit - 1) / ksplit;
-        ksplit = (f->n_stages + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, f->n_stages)), f->n_stages);
     if (ksplit > 1) {
-        int rc = dense_ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), stream);
+        int rc = dense_ensure_partials(m, (size_t)ksplit * call.n_frames * m->n_cols * sizeof(float), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit);
@@ -1078,34 +1075,33 @@ static int launch_fold_t(ltmi_masks *m, const float *tile, int64_t n_frames, int
                 LTMI_HIP(hipFuncSetAttribute((const void *)k8, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
                 attr8[m->device & 15] = true;
             }
-            hipLaunchKernelGGL(k8, grid, dim3(8 * 64), LDS, stream, tile, ld, n_frames, f->sig_w / FD_KB,
-                               (const int2 *)f->rows, (const float *)f->img, f->n_stages, out, ld_out, m->n_cols,
-                               (const int *)f->colmap, accumulate, dense_partial_sums(m), ksplit,
-                               (const unsigned char *)f->zeros, m->roi_rows);
+            hipLaunchKernelGGL(k8, grid, dim3(8 * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames,
+                               f->sig_w / FD_KB, (const int2 *)f->rows, (const float *)f->img, f->n_stages, out,
+                               call.ld_out, m->n_cols, (const int *)f->colmap, call.accumulate, dense_partial_sums(m),
+                               ksplit, (const unsigned char *)f->zeros, call.rows);
         }
     } else {
-        hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, stream, tile, ld, n_frames, f->sig_w / FD_KB,
-                           (const int2 *)f->rows, (const float *)f->img, f->n_stages, out, ld_out, m->n_cols,
-                           (const int *)f->colmap, accumulate, dense_partial_sums(m), in_turn ? -ksplit : ksplit,
-                           (const unsigned char *)f->zeros, m->roi_rows, (const int4 *)nullptr, (const int *)nullptr);
+        hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames,
+                           f->sig_w / FD_KB, (const int2 *)f->rows, (const float *)f->img, f->n_stages, out,
+                           call.ld_out, m->n_cols, (const int *)f->colmap, call.accumulate, dense_partial_sums(m),
+                           in_turn ? -ksplit : ksplit, (const unsigned char *)f->zeros, call.rows,
+                           (const int4 *)nullptr, (const int *)nullptr);
     }
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_fold%s<f,even=%d,odd=%d,rows %d+%d=%d%s%s> grid=(%u,%u)",
-             eight ? "8" : "", NGE, NGO, f->n_fold_rows, f->sig_h - f->n_fold_rows, f->c2, m->roi_rows ? ",rows" : "",
+             eight ? "8" : "", NGE, NGO, f->n_fold_rows, f->sig_h - f->n_fold_rows, f->c2, call.rows ? ",rows" : "",
              in_turn && !eight ? ",in turn" : "", grid.x, grid.y);
     if (ksplit > 1) {
-        const int rc = dense_reduce_partials(m, ksplit, n_frames, out, ld_out, accumulate, stream);
+        const int rc = dense_reduce_partials(m, ksplit, call.n_frames, out, call.ld_out, call.accumulate, call.stream);
         if (rc != LTMI_OK) return rc;
     }
     return LTMI_OK;
 }
 
-int ltmi::launch_fold(ltmi_masks *m, const float *tile, int64_t n_frames, int64_t ld, float *out, int64_t ld_out,
-                       int accumulate, hipStream_t stream) {
+int ltmi::launch_fold(ltmi_masks *m, const MaskCall &call) {
     const FoldImage *f = (const FoldImage *)m->fold;
-#define LTMI_FOLD_CASE(E_, O_)                                                                                 \
-    if (f->nge == E_ && f->ngo == O_)                                                                          \
-        return launch_fold_t<E_, O_>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+#define LTMI_FOLD_CASE(E_, O_) \
+    if (f->nge == E_ && f->ngo == O_) return launch_fold_t<E_, O_>(m, call);
     LTMI_FOLD_CASE(1, 0) LTMI_FOLD_CASE(2, 0) LTMI_FOLD_CASE(3, 0) LTMI_FOLD_CASE(4, 0)
     LTMI_FOLD_CASE(1, 1) LTMI_FOLD_CASE(2, 1) LTMI_FOLD_CASE(1, 2) LTMI_FOLD_CASE(2, 2)
 #undef LTMI_FOLD_CASE
@@ -1144,8 +1140,9 @@ bool ltmi::fold_takes16(ltmi_masks *m, const void *tile, int64_t ld, int px_byte
 }
 
 template <typename T, int NGE, int NGO>
-static int launch_fold16_t(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out, int64_t ld_out,
-                           int accumulate, hipStream_t stream) {
+static int launch_fold16_t(ltmi_masks *m, const MaskCall &call) {
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
     const FoldImage *f = (const FoldImage *)m->fold;
     auto kern = k_dense_fold16<T, NGE, NGO, false>;
     constexpr int LDS = ltmi::fold16_lds_bytes(NGE + NGO, (int)sizeof(T));
@@ -1154,54 +1151,44 @@ static int launch_fold16_t(ltmi_masks *m, const T *tile, int64_t n_frames, int64
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr_set[m->device & 15] = true;
     }
-    const int64_t gx = (n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
+    const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
     int ksplit = m->tune_ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx, f->n_stages16);
-    ksplit = std::max(1, std::min(ksplit, f->n_stages16));
-    {
-        const int per = (f->n_stages16 + ksplit - 1) / ksplit;
-        ksplit = (f->n_stages16 + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, f->n_stages16)), f->n_stages16);
     if (ksplit > 1) {
-        int rc = dense_ensure_partials(m, (size_t)ksplit * n_frames * m->n_cols * sizeof(float), stream);
+        int rc = dense_ensure_partials(m, (size_t)ksplit * call.n_frames * m->n_cols * sizeof(float), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit);
-    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, stream, tile, ld, n_frames, f->sig_w / FD16_KB,
-                       (const int2 *)f->rows, (const float *)f->img16, f->n_stages16, out, ld_out, m->n_cols,
-                       (const int *)f->colmap, accumulate, dense_partial_sums(m), ksplit,
-                       (const unsigned char *)f->zeros, m->roi_rows, (const int4 *)nullptr, (const int *)nullptr);
+    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames,
+                       f->sig_w / FD16_KB, (const int2 *)f->rows, (const float *)f->img16, f->n_stages16, out,
+                       call.ld_out, m->n_cols, (const int *)f->colmap, call.accumulate, dense_partial_sums(m), ksplit,
+                       (const unsigned char *)f->zeros, call.rows, (const int4 *)nullptr, (const int *)nullptr);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_fold16<%s,even=%d,odd=%d,rows %d+%d=%d%s> grid=(%u,%u)",
-             typeid(T).name(), NGE, NGO, f->n_fold_rows, f->sig_h - f->n_fold_rows, f->c2, m->roi_rows ? ",rows" : "",
+             typeid(T).name(), NGE, NGO, f->n_fold_rows, f->sig_h - f->n_fold_rows, f->c2, call.rows ? ",rows" : "",
              grid.x, grid.y);
     if (ksplit > 1) {
-        const int rc = dense_reduce_partials(m, ksplit, n_frames, out, ld_out, accumulate, stream);
+        const int rc = dense_reduce_partials(m, ksplit, call.n_frames, out, call.ld_out, call.accumulate, call.stream);
         if (rc != LTMI_OK) return rc;
     }
     return LTMI_OK;
 }
 
 template <typename T>
-static int launch_fold16_any(ltmi_masks *m, const T *tile, int64_t n_frames, int64_t ld, float *out, int64_t ld_out,
-                             int accumulate, hipStream_t stream) {
+static int launch_fold16_any(ltmi_masks *m, const MaskCall &call) {
     const FoldImage *f = (const FoldImage *)m->fold;
-#define LTMI_FOLD_CASE(E_, O_)                                                                                 \
-    if (f->nge == E_ && f->ngo == O_)                                                                          \
-        return launch_fold16_t<T, E_, O_>(m, tile, n_frames, ld, out, ld_out, accumulate, stream);
+#define LTMI_FOLD_CASE(E_, O_) \
+    if (f->nge == E_ && f->ngo == O_) return launch_fold16_t<T, E_, O_>(m, call);
     LTMI_FOLD_CASE(1, 0) LTMI_FOLD_CASE(2, 0) LTMI_FOLD_CASE(3, 0) LTMI_FOLD_CASE(4, 0)
     LTMI_FOLD_CASE(1, 1) LTMI_FOLD_CASE(2, 1) LTMI_FOLD_CASE(1, 2) LTMI_FOLD_CASE(2, 2)
 #undef LTMI_FOLD_CASE
     LTMI_FAIL(LTMI_E_INVALID, "k_dense_fold16: no kernel for %d + %d groups", f->nge, f->ngo);
 }
 
-int ltmi::launch_fold16(ltmi_masks *m, const void *tile, int px_bytes, bool is_signed, int64_t n_frames, int64_t ld,
-                        float *out, int64_t ld_out, int accumulate, hipStream_t stream) {
-    if (px_bytes == 1)
-        return is_signed ? launch_fold16_any<int8_t>(m, (const int8_t *)tile, n_frames, ld, out, ld_out, accumulate, stream)
-                         : launch_fold16_any<uint8_t>(m, (const uint8_t *)tile, n_frames, ld, out, ld_out, accumulate, stream);
-    return is_signed ? launch_fold16_any<int16_t>(m, (const int16_t *)tile, n_frames, ld, out, ld_out, accumulate, stream)
-                     : launch_fold16_any<uint16_t>(m, (const uint16_t *)tile, n_frames, ld, out, ld_out, accumulate, stream);
+int ltmi::launch_fold16(ltmi_masks *m, const MaskCall &call, int px_bytes, bool is_signed) {
+    if (px_bytes == 1) return is_signed ? launch_fold16_any<int8_t>(m, call) : launch_fold16_any<uint8_t>(m, call);
+    return is_signed ? launch_fold16_any<int16_t>(m, call) : launch_fold16_any<uint16_t>(m, call);
 }
 
 // ---- banded stacks: column blocks with a pixel support each (k_dense_fold<.., LIST>) -----------------------------
@@ -1694,8 +1681,9 @@ static int band_ksplit(const ltmi_masks *m, int64_t gx, int n_blocks, int n_stag
 }
 
 template <int NGE, int NGO>
-static int launch_band_t(ltmi_masks *m, const BandImage *b, const float *tile, int64_t n_frames, int64_t ld, float *out,
-                         int64_t ld_out, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_band_t(ltmi_masks *m, const BandImage *b, const MaskCall &call, int n_cols) {
+    const float *tile = (const float *)call.tile;
+    float *out = (float *)call.out;
     auto kern = k_dense_fold<NGE, NGO, 0, true>;
     constexpr int LDS = ltmi::fold_lds_bytes(NGE + NGO);
     static bool attr_set[16] = {false};
@@ -1703,32 +1691,34 @@ static int launch_band_t(ltmi_masks *m, const BandImage *b, const float *tile, i
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr_set[m->device & 15] = true;
     }
-    const int64_t gx = (n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
+    const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
     const int ksplit = band_ksplit(m, gx, b->n_blocks, b->n_stages);
     if (ksplit > 1) {
-        const int rc = dense_ensure_partials(m, (size_t)ksplit * n_frames * n_cols * sizeof(float), stream);
+        const int rc = dense_ensure_partials(m, (size_t)ksplit * call.n_frames * n_cols * sizeof(float), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)(b->n_blocks * ksplit));
-    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, stream, tile, ld, n_frames, b->sig_w / FD_KB,
-                       (const int2 *)nullptr, (const float *)b->img, b->n_stages, out, ld_out, n_cols,
-                       (const int *)b->colmap, accumulate, dense_partial_sums(m), ksplit,
-                       (const unsigned char *)b->zeros, m->roi_rows, (const int4 *)b->stages, (const int *)b->blk_off);
+    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames,
+                       b->sig_w / FD_KB, (const int2 *)nullptr, (const float *)b->img, b->n_stages, out, call.ld_out,
+                       n_cols, (const int *)b->colmap, call.accumulate, dense_partial_sums(m), ksplit,
+                       (const unsigned char *)b->zeros, call.rows, (const int4 *)b->stages, (const int *)b->blk_off);
     LTMI_HIP(hipGetLastError());
     if (ksplit > 1) {
-        const int rc = dense_reduce_partials(m, ksplit, n_frames, out, ld_out, accumulate, stream, n_cols);
+        const int rc = dense_reduce_partials(m, ksplit, call.n_frames, out, call.ld_out, call.accumulate, call.stream,
+                                             n_cols);
         if (rc != LTMI_OK) return rc;
     }
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_dense_fold<f,even=%d,odd=%d,banded: %d blocks, %d stages (x%.2f), rows %d+%d=%d%s> grid=(%u,%u)", NGE, NGO,
              b->n_blocks, b->n_stages, b->reread, b->n_fold_rows, b->sig_h - b->n_fold_rows, b->c2,
-             m->roi_rows ? ",rows" : "", grid.x, grid.y);
+             call.rows ? ",rows" : "", grid.x, grid.y);
     return LTMI_OK;
 }
 
 template <typename T, int NGE, int NGO>
-static int launch_band16_t(ltmi_masks *m, const BandImage *b, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                           int64_t ld_out, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_band16_t(ltmi_masks *m, const BandImage *b, const MaskCall &call, int n_cols) {
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
     auto kern = k_dense_fold16<T, NGE, NGO, true>;
     constexpr int LDS = ltmi::fold16_lds_bytes(NGE + NGO, (int)sizeof(T));
     static bool attr_set[16] = {false};
@@ -1736,60 +1726,52 @@ static int launch_band16_t(ltmi_masks *m, const BandImage *b, const T *tile, int
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr_set[m->device & 15] = true;
     }
-    const int64_t gx = (n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
+    const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
     const int ksplit = band_ksplit(m, gx, b->n_blocks, b->n_stages16);
     if (ksplit > 1) {
-        const int rc = dense_ensure_partials(m, (size_t)ksplit * n_frames * n_cols * sizeof(float), stream);
+        const int rc = dense_ensure_partials(m, (size_t)ksplit * call.n_frames * n_cols * sizeof(float), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)(b->n_blocks * ksplit));
-    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, stream, tile, ld, n_frames, b->sig_w / FD16_KB,
-                       (const int2 *)nullptr, (const float *)b->img16, b->n_stages16, out, ld_out, n_cols,
-                       (const int *)b->colmap, accumulate, dense_partial_sums(m), ksplit,
-                       (const unsigned char *)b->zeros, m->roi_rows, (const int4 *)b->stages16,
+    hipLaunchKernelGGL(kern, grid, dim3(FD_WAVES * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames,
+                       b->sig_w / FD16_KB, (const int2 *)nullptr, (const float *)b->img16, b->n_stages16, out,
+                       call.ld_out, n_cols, (const int *)b->colmap, call.accumulate, dense_partial_sums(m), ksplit,
+                       (const unsigned char *)b->zeros, call.rows, (const int4 *)b->stages16,
                        (const int *)b->blk_off16);
     LTMI_HIP(hipGetLastError());
     if (ksplit > 1) {
-        const int rc = dense_reduce_partials(m, ksplit, n_frames, out, ld_out, accumulate, stream, n_cols);
+        const int rc = dense_reduce_partials(m, ksplit, call.n_frames, out, call.ld_out, call.accumulate, call.stream,
+                                             n_cols);
         if (rc != LTMI_OK) return rc;
     }
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_dense_fold16<%s,even=%d,odd=%d,banded: %d blocks, %d stages (x%.2f), rows %d+%d=%d%s> grid=(%u,%u)",
              typeid(T).name(), NGE, NGO, b->n_blocks, b->n_stages16, b->reread16, b->n_fold_rows,
-             b->sig_h - b->n_fold_rows, b->c2, m->roi_rows ? ",rows" : "", grid.x, grid.y);
+             b->sig_h - b->n_fold_rows, b->c2, call.rows ? ",rows" : "", grid.x, grid.y);
     return LTMI_OK;
 }
 
 template <typename T>
-static int band_apply16(ltmi_masks *m, const BandImage *b, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                        int64_t ld_out, int n_cols, int accumulate, hipStream_t stream) {
-#define LTMI_BAND_CASE(E_, O_)                                                                                 \
-    if (b->nge == E_ && b->ngo == O_)                                                                          \
-        return launch_band16_t<T, E_, O_>(m, b, tile, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
+static int band_apply16(ltmi_masks *m, const BandImage *b, const MaskCall &call, int n_cols) {
+#define LTMI_BAND_CASE(E_, O_) \
+    if (b->nge == E_ && b->ngo == O_) return launch_band16_t<T, E_, O_>(m, b, call, n_cols);
     LTMI_BAND_CASE(1, 0) LTMI_BAND_CASE(2, 0) LTMI_BAND_CASE(1, 1) LTMI_BAND_CASE(2, 1) LTMI_BAND_CASE(1, 2)
     LTMI_BAND_CASE(2, 2)
 #undef LTMI_BAND_CASE
     LTMI_FAIL(LTMI_E_INVALID, "k_dense_fold16 (banded): no kernel for %d + %d groups", b->nge, b->ngo);
 }
 
-int ltmi::band_apply(ltmi_masks *m, void *band, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld,
-                     float *out, int64_t ld_out, int n_cols, int accumulate, hipStream_t stream) {
+int ltmi::band_apply(ltmi_masks *m, void *band, const MaskCall &call, int n_cols) {
     const BandImage *b = (const BandImage *)band;
-    switch (tile_dtype) {
-        case LTMI_U8:
-            return band_apply16<uint8_t>(m, b, (const uint8_t *)tile, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
-        case LTMI_I8:
-            return band_apply16<int8_t>(m, b, (const int8_t *)tile, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
-        case LTMI_U16:
-            return band_apply16<uint16_t>(m, b, (const uint16_t *)tile, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
-        case LTMI_I16:
-            return band_apply16<int16_t>(m, b, (const int16_t *)tile, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
+    switch (call.tile_dtype) {
+        case LTMI_U8: return band_apply16<uint8_t>(m, b, call, n_cols);
+        case LTMI_I8: return band_apply16<int8_t>(m, b, call, n_cols);
+        case LTMI_U16: return band_apply16<uint16_t>(m, b, call, n_cols);
+        case LTMI_I16: return band_apply16<int16_t>(m, b, call, n_cols);
         default: break;
     }
-    const float *ft = (const float *)tile;
-#define LTMI_BAND_CASE(E_, O_)                                                                                 \
-    if (b->nge == E_ && b->ngo == O_)                                                                          \
-        return launch_band_t<E_, O_>(m, b, ft, n_frames, ld, out, ld_out, n_cols, accumulate, stream);
+#define LTMI_BAND_CASE(E_, O_) \
+    if (b->nge == E_ && b->ngo == O_) return launch_band_t<E_, O_>(m, b, call, n_cols);
     LTMI_BAND_CASE(1, 0) LTMI_BAND_CASE(2, 0) LTMI_BAND_CASE(1, 1) LTMI_BAND_CASE(2, 1) LTMI_BAND_CASE(1, 2)
     LTMI_BAND_CASE(2, 2)
 #undef LTMI_BAND_CASE

@@ -306,15 +306,20 @@ bool guard_wanted_shifted(const ltmi_masks *m, int tile_dtype) {
                                m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128);
 }
 
-int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, void *out,
-                int64_t ld_out, int accumulate, hipStream_t stream) {
+int guard_apply(ltmi_masks *m, const MaskCall &call) {
+    const int64_t n_frames = call.n_frames, ld_tile = call.ld_tile;
+    hipStream_t stream = call.stream;
     const size_t elem = (size_t)dtype_size(m->result_dtype);
     void *target = nullptr;
     int64_t ld_t = 0;
-    int rc = guard_target(m, n_frames, out, ld_out, accumulate, stream, &target, &ld_t);
+    int rc = guard_target(m, n_frames, call.out, call.ld_out, call.accumulate, stream, &target, &ld_t);
     if (rc != LTMI_OK) return rc;
     NfGuard *g = (NfGuard *)m->guard;
-    rc = apply_masks_unguarded(m, tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream);
+    MaskCall product = call;                                // (into the guard's scratch under `accumulate`)
+    product.out = target;
+    product.ld_out = ld_t;
+    product.accumulate = 0;
+    rc = apply_masks_unguarded(m, product);
     if (rc != LTMI_OK) return rc;
     const bool exact = m->kind == 2 && m->last_exact && !m->dense_origin;   // the gather kernel ran: nothing to check
     g->last_checked = !exact;
@@ -327,31 +332,31 @@ int guard_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frame
         rc = guard_list_rows(m, target, ld_t, n_frames, stream, &ctl, &list);
         if (rc != LTMI_OK) return rc;
         if (DenseOrigin *d = (DenseOrigin *)m->dense_origin) {
-            if (tile_dtype != LTMI_F32 || f64)
+            if (call.tile_dtype != LTMI_F32 || f64)
                 LTMI_FAIL(LTMI_E_DTYPE, "a dense stack held as CSR takes float32 frames and float32 / complex64 results");
-            const float *t = (const float *)tile;
+            const float *t = (const float *)call.tile;
             if (d->n_unstored > 0) {
                 hipLaunchKernelGGL(k_scan_unstored<float>, dim3((unsigned)n_frames), dim3(256), 0, stream, t, ld_tile,
-                                   n_frames, m->roi_rows, (const int32_t *)d->unstored, d->n_unstored, ctl, list);
+                                   n_frames, call.rows, (const int32_t *)d->unstored, d->n_unstored, ctl, list);
                 LTMI_HIP(hipGetLastError());
             }
             const size_t lds = (size_t)(m->n_masks + 1) * sizeof(int);
             const unsigned blocks = (unsigned)std::min<int64_t>(n_frames, 2048);
             hipLaunchKernelGGL(k_dense_fixup<float>, dim3(blocks), dim3(256), lds, stream, t, ld_tile, m->n_px,
-                               m->roi_rows, (const int32_t *)d->indptr, (const int32_t *)d->indices, (int)m->n_masks,
+                               call.rows, (const int32_t *)d->indptr, (const int32_t *)d->indices, (int)m->n_masks,
                                cplx ? 2 : 1, (float *)target, ld_real, (const int *)ctl, (const int32_t *)list);
             LTMI_HIP(hipGetLastError());
         } else {
             ltmi_masks *redo = m->sparse_origin ? m->sparse_origin : m;
             // (the row in bytes is the same for both handles; a complex128 stack's gather image counts float64 columns)
-            const int64_t ld_redo = ld_t * (int64_t)elem / dtype_size(redo->result_dtype);
-            rc = csr_redo(redo, tile, tile_dtype, n_frames, ld_tile, target, ld_redo, list, ctl, m->roi_rows, stream);
+            product.ld_out = ld_t * (int64_t)elem / dtype_size(redo->result_dtype);
+            rc = csr_redo(redo, product, list, ctl);
             if (rc != LTMI_OK) return rc;
         }
         const size_t len = strlen(m->last_kernel);
         snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
     }
-    return guard_deliver(m, out, ld_out, n_frames, accumulate, stream);
+    return guard_deliver(m, call.out, call.ld_out, n_frames, call.accumulate, stream);
 }
 
 }  // namespace ltmi

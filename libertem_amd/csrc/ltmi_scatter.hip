@@ -605,8 +605,9 @@ void *scat_build(const int64_t *indptr, const int64_t *indices, const float *val
 }
 
 template <typename T>
-static int launch_scatter(ltmi_masks *m, ScatImage *b, const T *tile, int64_t n_frames, int64_t ld, float *out,
-                          int64_t ld_out_f, int n_cols, int accumulate, hipStream_t stream) {
+static int launch_scatter(ltmi_masks *m, ScatImage *b, const MaskCall &call, int n_cols) {   // call.ld_out in floats
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
     auto kern = k_scatter<T>;
     int abl = 0;
     if constexpr (std::is_same<T, uint16_t>::value) {
@@ -626,33 +627,33 @@ static int launch_scatter(ltmi_masks *m, ScatImage *b, const T *tile, int64_t n_
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS));
         set[m->device & 15][abl] = true;
     }
-    dim3 grid((unsigned)((n_frames + SC_FB - 1) / SC_FB), (unsigned)b->n_pass);
-    hipLaunchKernelGGL(kern, grid, dim3(SC_WAVES * 64), SC_LDS, stream, tile, ld, n_frames,
+    dim3 grid((unsigned)((call.n_frames + SC_FB - 1) / SC_FB), (unsigned)b->n_pass);
+    hipLaunchKernelGGL(kern, grid, dim3(SC_WAVES * 64), SC_LDS, call.stream, tile, call.ld_tile, call.n_frames,
                        (const uint32_t *)b->hdr, (const float *)b->wts, (const int64_t *)b->stream_off,
                        (const int32_t *)b->n_blk, (const int32_t *)b->dma_off, (const int32_t *)b->active_off,
-                       (const int32_t *)b->col_of_slot, out, ld_out_f, n_cols, accumulate, m->roi_rows);
+                       (const int32_t *)b->col_of_slot, out, call.ld_out, n_cols, call.accumulate, call.rows);
     LTMI_HIP(hipGetLastError());
     if (b->n_tail > 0) {
-        hipLaunchKernelGGL(k_scatter_tail<T>, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, stream,
-                           tile, ld, n_frames, (const int32_t *)b->tail_px, (const int32_t *)b->tail_col,
-                           (const float *)b->tail_val, b->n_tail, out, ld_out_f, m->roi_rows);
+        hipLaunchKernelGGL(k_scatter_tail<T>, dim3((unsigned)((call.n_frames + 255) / 256)), dim3(256), 0, call.stream,
+                           tile, call.ld_tile, call.n_frames, (const int32_t *)b->tail_px, (const int32_t *)b->tail_col,
+                           (const float *)b->tail_val, b->n_tail, out, call.ld_out, call.rows);
         LTMI_HIP(hipGetLastError());
     }
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_scatter<%s%s> grid=(%u,%u) blocks=%zu fill=%.2f crit=%ld", typeid(T).name(),
-             m->roi_rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->fill, b->crit_blocks);
+             call.rows ? ",rows" : "", grid.x, grid.y, b->n_blocks, b->fill, b->crit_blocks);
     return LTMI_OK;
 }
 
 // handled = false: the tile does not meet the kernel's rules (the caller goes on to the other sparse kernels)
-int scat_apply(ltmi_masks *m, void *set, int cplx, const void *tile, int tile_dtype, int64_t n_frames,
-               int64_t ld_tile, void *out, int64_t ld_out, int accumulate, hipStream_t stream, bool *handled) {
+int scat_apply(ltmi_masks *m, void *set, int cplx, const MaskCall &call, bool *handled) {
     ScatSet *s = (ScatSet *)set;
     *handled = false;
-    if (!s || n_frames <= 0) return LTMI_OK;
+    if (!s || call.n_frames <= 0) return LTMI_OK;
+    const int tile_dtype = call.tile_dtype;
     const int sz = dtype_size(tile_dtype);
     if (!(sz == 1 || sz == 2 || sz == 4) || tile_dtype == LTMI_U32 || tile_dtype == LTMI_I32) return LTMI_OK;
-    if (!vector_loads_ok(tile, ld_tile, (size_t)sz)) return LTMI_OK;
+    if (!vector_loads_ok(call.tile, call.ld_tile, (size_t)sz)) return LTMI_OK;
     if (s->n_px * sz > 0x7fffffff) return LTMI_OK;                       // (row offsets are 31-bit)
     const int slot = sz == 1 ? 0 : (sz == 2 ? 1 : 2);
     if (!s->img[slot]) {
@@ -670,16 +671,16 @@ int scat_apply(ltmi_masks *m, void *set, int cplx, const void *tile, int tile_dt
     ScatImage *b = s->img[slot];
     const int nc = cplx ? 2 : 1;
     const int n_cols = (int)(m->n_masks * nc);
-    float *o = (float *)out;
-    const int64_t ldo = ld_out * nc;
+    MaskCall f32 = call;
+    f32.ld_out = call.ld_out * nc;
     *handled = true;
     switch (tile_dtype) {
         case LTMI_BOOL:
-        case LTMI_U8: return launch_scatter<uint8_t>(m, b, (const uint8_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_I8: return launch_scatter<int8_t>(m, b, (const int8_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_U16: return launch_scatter<uint16_t>(m, b, (const uint16_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_I16: return launch_scatter<int16_t>(m, b, (const int16_t *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
-        case LTMI_F32: return launch_scatter<float>(m, b, (const float *)tile, n_frames, ld_tile, o, ldo, n_cols, accumulate, stream);
+        case LTMI_U8: return launch_scatter<uint8_t>(m, b, f32, n_cols);
+        case LTMI_I8: return launch_scatter<int8_t>(m, b, f32, n_cols);
+        case LTMI_U16: return launch_scatter<uint16_t>(m, b, f32, n_cols);
+        case LTMI_I16: return launch_scatter<int16_t>(m, b, f32, n_cols);
+        case LTMI_F32: return launch_scatter<float>(m, b, f32, n_cols);
     }
     *handled = false;
     return LTMI_OK;

@@ -356,19 +356,20 @@ static int sell_set_lds(KERN kern, int device, size_t lds, bool *set) {
 }
 
 template <typename T>
-static int launch_sell(ltmi_masks *m, CsrImage *c, const T *tile, int64_t n_frames, int64_t ld,
-                       float *out, int64_t ld_out_f, int accumulate, hipStream_t stream,
-                       const int32_t *sel = nullptr, const int *n_sel = nullptr) {
-    const int vec_ok = vector_loads_ok(tile, ld, sizeof(T)) ? 1 : 0;
+static int launch_sell(ltmi_masks *m, CsrImage *c, const MaskCall &call, const int32_t *sel = nullptr,
+                       const int *n_sel = nullptr) {       // call.ld_out in floats
+    const T *tile = (const T *)call.tile;
+    float *out = (float *)call.out;
+    const int vec_ok = vector_loads_ok(tile, call.ld_tile, sizeof(T)) ? 1 : 0;
     const char *abl = getenv("LTMI_SELL_ABLATE");     // 1: loader only, 2: gathers only (bench)
     const int ablate = abl ? atoi(abl) : 0;
-    dim3 grid((unsigned)((n_frames + SP_F - 1) / SP_F), (unsigned)c->n_pass);
+    dim3 grid((unsigned)((call.n_frames + SP_F - 1) / SP_F), (unsigned)c->n_pass);
     // + one all-zero pixel row (index SP_P) for the padding entries of the image
     const size_t lds = (size_t)(SP_P + 1) * SP_F * sizeof(float);
     const int nc = c->cplx ? 2 : 1;
     if (sel) {
         const int split = sell_redo_split(c);
-        hipLaunchKernelGGL(k_zero_sel_rows<float>, dim3(256), dim3(256), 0, stream, out, ld_out_f,
+        hipLaunchKernelGGL(k_zero_sel_rows<float>, dim3(256), dim3(256), 0, call.stream, out, call.ld_out,
                            (int)m->n_masks * nc, sel, n_sel);
         LTMI_HIP(hipGetLastError());
         int rc;
@@ -376,20 +377,20 @@ static int launch_sell(ltmi_masks *m, CsrImage *c, const T *tile, int64_t n_fram
             auto kern = k_sell_apply<T, 2, true, float, true>;
             static bool set[16] = {false};
             if ((rc = sell_set_lds(kern, m->device, lds, set)) != LTMI_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
-                               (const uint32_t *)c->pix, (const float *)c->val, (const int *)c->row_off,
-                               (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                               c->n_chunks, out, ld_out_f, (int)m->n_masks, 0, vec_ok, 0, m->roi_rows, sel, n_sel,
-                               c->n_pass, split);
+            hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, call.stream, tile, call.ld_tile,
+                               call.n_frames, m->n_px, (const uint32_t *)c->pix, (const float *)c->val,
+                               (const int *)c->row_off, (const int *)c->row_len, (const int *)c->active,
+                               (const int *)c->active_off, c->n_chunks, out, call.ld_out, (int)m->n_masks, 0, vec_ok,
+                               0, call.rows, sel, n_sel, c->n_pass, split);
         } else {
             auto kern = k_sell_apply<T, 4, false, float, true>;
             static bool set[16] = {false};
             if ((rc = sell_set_lds(kern, m->device, lds, set)) != LTMI_OK) return rc;
-            hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
-                               (const uint32_t *)c->pix, (const float *)c->val, (const int *)c->row_off,
-                               (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                               c->n_chunks, out, ld_out_f, (int)m->n_masks, 0, vec_ok, 0, m->roi_rows, sel, n_sel,
-                               c->n_pass, split);
+            hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, call.stream, tile, call.ld_tile,
+                               call.n_frames, m->n_px, (const uint32_t *)c->pix, (const float *)c->val,
+                               (const int *)c->row_off, (const int *)c->row_len, (const int *)c->active,
+                               (const int *)c->active_off, c->n_chunks, out, call.ld_out, (int)m->n_masks, 0, vec_ok,
+                               0, call.rows, sel, n_sel, c->n_pass, split);
         }
         LTMI_HIP(hipGetLastError());
         return LTMI_OK;                                   // (a redo keeps the name of the kernel it follows)
@@ -399,51 +400,52 @@ static int launch_sell(ltmi_masks *m, CsrImage *c, const T *tile, int64_t n_fram
         static bool set[16] = {false};
         const int rc = sell_set_lds(kern, m->device, lds, set);
         if (rc != LTMI_OK) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
+        hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                            (const uint32_t *)c->pix, (const float *)c->val, (const int *)c->row_off,
                            (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                           c->n_chunks, out, ld_out_f, (int)m->n_masks, accumulate, vec_ok, ablate, m->roi_rows,
+                           c->n_chunks, out, call.ld_out, (int)m->n_masks, call.accumulate, vec_ok, ablate, call.rows,
                            (const int32_t *)nullptr, (const int *)nullptr, c->n_pass, 1);
     } else {
         auto kern = k_sell_apply<T, 4, false>;
         static bool set[16] = {false};
         const int rc = sell_set_lds(kern, m->device, lds, set);
         if (rc != LTMI_OK) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
+        hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                            (const uint32_t *)c->pix, (const float *)c->val, (const int *)c->row_off,
                            (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                           c->n_chunks, out, ld_out_f, (int)m->n_masks, accumulate, vec_ok, ablate, m->roi_rows,
+                           c->n_chunks, out, call.ld_out, (int)m->n_masks, call.accumulate, vec_ok, ablate, call.rows,
                            (const int32_t *)nullptr, (const int *)nullptr, c->n_pass, 1);
     }
     LTMI_HIP(hipGetLastError());
     m->last_exact = true;                                 // only stored entries were multiplied
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_sell_apply<%s,%s%s> grid=(%u,%u) rows=%zu",
-             typeid(T).name(), c->cplx ? "c64" : "f32", m->roi_rows ? ",rows" : "", grid.x, grid.y,
+             typeid(T).name(), c->cplx ? "c64" : "f32", call.rows ? ",rows" : "", grid.x, grid.y,
              c->n_rows);
     return LTMI_OK;
 }
 
 // float64 results: the same kernel with double slab / accumulators / values (128 KiB of LDS)
 template <typename T>
-static int launch_sell64(ltmi_masks *m, CsrImage *c, const T *tile, int64_t n_frames, int64_t ld,
-                         double *out, int64_t ld_out, int accumulate, hipStream_t stream,
-                         const int32_t *sel = nullptr, const int *n_sel = nullptr) {
-    const int vec_ok = vector_loads_ok(tile, ld, sizeof(T)) ? 1 : 0;
-    dim3 grid((unsigned)((n_frames + SP_F - 1) / SP_F), (unsigned)c->n_pass);
+static int launch_sell64(ltmi_masks *m, CsrImage *c, const MaskCall &call, const int32_t *sel = nullptr,
+                         const int *n_sel = nullptr) {
+    const T *tile = (const T *)call.tile;
+    double *out = (double *)call.out;
+    const int vec_ok = vector_loads_ok(tile, call.ld_tile, sizeof(T)) ? 1 : 0;
+    dim3 grid((unsigned)((call.n_frames + SP_F - 1) / SP_F), (unsigned)c->n_pass);
     const size_t lds = (size_t)(SP_P + 1) * SP_F * sizeof(double);
     if (sel) {
-        hipLaunchKernelGGL(k_zero_sel_rows<double>, dim3(256), dim3(256), 0, stream, out, ld_out, (int)m->n_masks,
-                           sel, n_sel);
+        hipLaunchKernelGGL(k_zero_sel_rows<double>, dim3(256), dim3(256), 0, call.stream, out, call.ld_out,
+                           (int)m->n_masks, sel, n_sel);
         LTMI_HIP(hipGetLastError());
         auto kern = k_sell_apply<T, 4, false, double, true>;
         static bool set[16] = {false};
         const int rc = sell_set_lds(kern, m->device, lds, set);
         if (rc != LTMI_OK) return rc;
-        hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
-                           (const uint32_t *)c->pix, (const double *)c->val64, (const int *)c->row_off,
-                           (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                           c->n_chunks, out, ld_out, (int)m->n_masks, 0, vec_ok, 0, m->roi_rows, sel, n_sel,
-                           c->n_pass, sell_redo_split(c));
+        hipLaunchKernelGGL(kern, dim3(SELL_REDO_WGS), dim3(SP_NT), lds, call.stream, tile, call.ld_tile,
+                           call.n_frames, m->n_px, (const uint32_t *)c->pix, (const double *)c->val64,
+                           (const int *)c->row_off, (const int *)c->row_len, (const int *)c->active,
+                           (const int *)c->active_off, c->n_chunks, out, call.ld_out, (int)m->n_masks, 0, vec_ok, 0,
+                           call.rows, sel, n_sel, c->n_pass, sell_redo_split(c));
         LTMI_HIP(hipGetLastError());
         return LTMI_OK;
     }
@@ -451,15 +453,15 @@ static int launch_sell64(ltmi_masks *m, CsrImage *c, const T *tile, int64_t n_fr
     static bool set[16] = {false};
     const int rc = sell_set_lds(kern, m->device, lds, set);
     if (rc != LTMI_OK) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, stream, tile, ld, n_frames, m->n_px,
+    hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                        (const uint32_t *)c->pix, (const double *)c->val64, (const int *)c->row_off,
                        (const int *)c->row_len, (const int *)c->active, (const int *)c->active_off,
-                       c->n_chunks, out, ld_out, (int)m->n_masks, accumulate, vec_ok, 0, m->roi_rows,
+                       c->n_chunks, out, call.ld_out, (int)m->n_masks, call.accumulate, vec_ok, 0, call.rows,
                        (const int32_t *)nullptr, (const int *)nullptr, c->n_pass, 1);
     LTMI_HIP(hipGetLastError());
     m->last_exact = true;
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_sell_apply<%s,f64%s> grid=(%u,%u) rows=%zu",
-             typeid(T).name(), m->roi_rows ? ",rows" : "", grid.x, grid.y, c->n_rows);
+             typeid(T).name(), call.rows ? ",rows" : "", grid.x, grid.y, c->n_rows);
     return LTMI_OK;
 }
 
@@ -526,10 +528,33 @@ bool csr_has_band(const ltmi_masks *m) {
 // float32 frames: k_scatter only where the blocked image pads at least this much (per stored entry)
 static constexpr double SCAT_MIN_BELL_RATIO = 3.0;
 
-int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
-              void *out, int64_t ld_out, int accumulate, hipStream_t stream) {
+// float64 results, and the exact float64 sums behind integer results
+static int csr_apply_f64(ltmi_masks *m, CsrImage *c, const MaskCall &call) {
+    switch (call.tile_dtype) {
+        case LTMI_BOOL:
+        case LTMI_U8: return launch_sell64<uint8_t>(m, c, call);
+        case LTMI_I8: return launch_sell64<int8_t>(m, c, call);
+        case LTMI_U16: return launch_sell64<uint16_t>(m, c, call);
+        case LTMI_I16: return launch_sell64<int16_t>(m, c, call);
+        case LTMI_U32: return launch_sell64<uint32_t>(m, c, call);
+        case LTMI_I32: return launch_sell64<int32_t>(m, c, call);
+        case LTMI_U64: return launch_sell64<uint64_t>(m, c, call);
+        case LTMI_I64: return launch_sell64<int64_t>(m, c, call);
+        case LTMI_F32: return launch_sell64<float>(m, c, call);
+        case LTMI_F64: return launch_sell64<double>(m, c, call);
+    }
+    LTMI_FAIL(LTMI_E_DTYPE, "sparse masks with float64 results: tile dtype %s is not supported",
+              dtype_name(call.tile_dtype));
+}
+
+int csr_apply(ltmi_masks *m, const MaskCall &call) {
     CsrImage *c = (CsrImage *)m->csr;
-    if (m->roi_rows && !csr_rows_ok(m, tile, tile_dtype, ld_tile))
+    const void *tile = call.tile;
+    const int tile_dtype = call.tile_dtype, accumulate = call.accumulate;
+    const int64_t n_frames = call.n_frames, ld_tile = call.ld_tile, ld_out = call.ld_out;
+    void *out = call.out;
+    hipStream_t stream = call.stream;
+    if (call.rows && !csr_rows_ok(m, tile, tile_dtype, ld_tile))
         LTMI_FAIL(LTMI_E_INVALID, "sparse masks: this handle / tile cannot take a row list");
     if (c->int_result) {
         // exact in float64 -> gather into a float64 scratch, then truncate to the result width
@@ -547,10 +572,11 @@ int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
             LTMI_HIP(hipMalloc(&m->res64, need));
             m->res64_bytes = need;
         }
-        c->int_result = 0;                                  // (the float64 branch below, once)
-        const int rc = csr_apply(m, tile, tile_dtype, n_frames, ld_tile, m->res64, m->n_masks, 0,
-                                 stream);
-        c->int_result = 1;
+        MaskCall sums = call;
+        sums.out = m->res64;
+        sums.ld_out = m->n_masks;
+        sums.accumulate = 0;
+        const int rc = csr_apply_f64(m, c, sums);
         if (rc != LTMI_OK) return rc;
         const int64_t n = n_frames * m->n_masks;
         const dim3 grid((unsigned)((n + 255) / 256));
@@ -566,24 +592,7 @@ int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
         snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " exact-int");
         return LTMI_OK;
     }
-    if (c->f64) {
-        double *o = (double *)out;
-        switch (tile_dtype) {
-            case LTMI_BOOL:
-            case LTMI_U8: return launch_sell64<uint8_t>(m, c, (const uint8_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_I8: return launch_sell64<int8_t>(m, c, (const int8_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_U16: return launch_sell64<uint16_t>(m, c, (const uint16_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_I16: return launch_sell64<int16_t>(m, c, (const int16_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_U32: return launch_sell64<uint32_t>(m, c, (const uint32_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_I32: return launch_sell64<int32_t>(m, c, (const int32_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_U64: return launch_sell64<uint64_t>(m, c, (const uint64_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_I64: return launch_sell64<int64_t>(m, c, (const int64_t *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_F32: return launch_sell64<float>(m, c, (const float *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-            case LTMI_F64: return launch_sell64<double>(m, c, (const double *)tile, n_frames, ld_tile, o, ld_out, accumulate, stream);
-        }
-        LTMI_FAIL(LTMI_E_DTYPE, "sparse masks with float64 results: tile dtype %s is not supported",
-                  dtype_name(tile_dtype));
-    }
+    if (c->f64) return csr_apply_f64(m, c, call);
     // one float32 FMA per stored entry on the vector ALUs (k_scatter; tuning 41: SELL kernel, 42: blocked image)
     // (float32 frames by default -- measured 7 % ahead of the float32 blocked image on C4, and a non-finite
     // pixel reaches fewer foreign masks; 1- / 2-byte pixels stay on the blocked images, which are 15 - 30 %
@@ -592,9 +601,10 @@ int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
         band_free_csr(c->kept);
         c->kept = nullptr;
     }
+    MaskCall f32 = call;                                  // (complex64 rows as 2 floats per mask)
+    f32.ld_out = ld_out * (c->cplx ? 2 : 1);
     if (c->band && band_takes(c->band, m, tile, tile_dtype, ld_tile))
-        return band_apply(m, c->band, tile, tile_dtype, n_frames, ld_tile, (float *)out,
-                          ld_out * (c->cplx ? 2 : 1), (int)(m->n_masks * (c->cplx ? 2 : 1)), accumulate, stream);
+        return band_apply(m, c->band, f32, (int)(m->n_masks * (c->cplx ? 2 : 1)));
     // ... unless the blocked image is well filled: a stack of dense column blocks (radial Fourier with several bins:
     // 1.3 padded MACs per stored entry) runs 3 x faster on the matrix cores (21 ms against 62 ms per 8192 frames
     // of 1024 x 1024, scripts/bench_second_runs.py); C4's rings (4.8) stay here
@@ -602,26 +612,22 @@ int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
     if (c->scat && (c->scat_all || tile_dtype == LTMI_F32) && !bell_better && m->tune_ksplit_ring != 41 &&
         m->tune_ksplit_ring != 42) {
         bool handled = false;
-        const int rc = scat_apply(m, c->scat, c->cplx, tile, tile_dtype, n_frames, ld_tile, out, ld_out,
-                                  accumulate, stream, &handled);
+        const int rc = scat_apply(m, c->scat, c->cplx, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
     // localised stacks: blocked image on the matrix cores (set_tuning 41 forces the SELL kernel)
     if (c->bell && m->tune_ksplit_ring != 41) {
         bool handled = false;
-        const int rc = bell_apply(m, c->bell, c->cplx, tile, tile_dtype, n_frames, ld_tile, out,
-                                  ld_out, accumulate, stream, &handled);
+        const int rc = bell_apply(m, c->bell, c->cplx, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
-    float *o = (float *)out;
-    const int64_t ldo = ld_out * (c->cplx ? 2 : 1);
     switch (tile_dtype) {
         case LTMI_BOOL:
-        case LTMI_U8: return launch_sell<uint8_t>(m, c, (const uint8_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-        case LTMI_I8: return launch_sell<int8_t>(m, c, (const int8_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-        case LTMI_U16: return launch_sell<uint16_t>(m, c, (const uint16_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-        case LTMI_I16: return launch_sell<int16_t>(m, c, (const int16_t *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
-        case LTMI_F32: return launch_sell<float>(m, c, (const float *)tile, n_frames, ld_tile, o, ldo, accumulate, stream);
+        case LTMI_U8: return launch_sell<uint8_t>(m, c, f32);
+        case LTMI_I8: return launch_sell<int8_t>(m, c, f32);
+        case LTMI_U16: return launch_sell<uint16_t>(m, c, f32);
+        case LTMI_I16: return launch_sell<int16_t>(m, c, f32);
+        case LTMI_F32: return launch_sell<float>(m, c, f32);
     }
     LTMI_FAIL(LTMI_E_DTYPE, "sparse masks: tile dtype %s is not supported with result dtype %s "
               "(supported tiles: uint8 int8 uint16 int16 float32)", dtype_name(tile_dtype),
@@ -631,23 +637,21 @@ int csr_apply(ltmi_masks *m, const void *tile, int tile_dtype, int64_t n_frames,
 
 // The frames `sel[0 .. *n_sel)` of a product again, on the gather kernel -- stored entries only, like the reference's
 // CSR loop (common/numba/__init__.py:153-184) -- written over their result rows (ltmi_guard.hip: frames whose
-// results came out non-finite on a kernel that also multiplies padding zeros).  The launch covers `max_frames`.
-int csr_redo(ltmi_masks *m, const void *tile, int tile_dtype, int64_t max_frames, int64_t ld_tile, void *out,
-             int64_t ld_out, const int32_t *sel, const int *n_sel, const int32_t *roi_rows, hipStream_t stream) {
+// results came out non-finite on a kernel that also multiplies padding zeros).  The launch covers `call.n_frames`.
+int csr_redo(ltmi_masks *m, const MaskCall &call, const int32_t *sel, const int *n_sel) {
     CsrImage *c = m ? (CsrImage *)m->csr : nullptr;
     if (!c || c->int_result) LTMI_FAIL(LTMI_E_INVALID, "csr_redo: not a float sparse handle");
-    const int32_t *keep = m->roi_rows;
-    m->roi_rows = roi_rows;
+    const int tile_dtype = call.tile_dtype;
+    MaskCall redo = call;
+    redo.accumulate = 0;
     int rc = LTMI_E_DTYPE;
     if (c->f64) {
-        double *o = (double *)out;
-        if (tile_dtype == LTMI_F32) rc = launch_sell64<float>(m, c, (const float *)tile, max_frames, ld_tile, o, ld_out, 0, stream, sel, n_sel);
-        else if (tile_dtype == LTMI_F64) rc = launch_sell64<double>(m, c, (const double *)tile, max_frames, ld_tile, o, ld_out, 0, stream, sel, n_sel);
+        if (tile_dtype == LTMI_F32) rc = launch_sell64<float>(m, c, redo, sel, n_sel);
+        else if (tile_dtype == LTMI_F64) rc = launch_sell64<double>(m, c, redo, sel, n_sel);
     } else if (tile_dtype == LTMI_F32) {
-        rc = launch_sell<float>(m, c, (const float *)tile, max_frames, ld_tile, (float *)out,
-                                ld_out * (c->cplx ? 2 : 1), 0, stream, sel, n_sel);
+        redo.ld_out = call.ld_out * (c->cplx ? 2 : 1);
+        rc = launch_sell<float>(m, c, redo, sel, n_sel);
     }
-    m->roi_rows = keep;
     if (rc == LTMI_E_DTYPE) LTMI_FAIL(LTMI_E_DTYPE, "csr_redo: %s tiles against %s results", dtype_name(tile_dtype),
                                       dtype_name(m->result_dtype));
     return rc;
@@ -667,20 +671,9 @@ bool csr_is_f64(const ltmi_masks *m) {
 
 }  // namespace ltmi
 
-static thread_local bool g_gather_only = false;
-
-extern "C" int ltmi_masks_create_csr_gather(int device, const int64_t *indptr, const int64_t *indices,
-                                            const void *data, int result_dtype, int64_t n_px,
-                                            int64_t n_masks, ltmi_masks **out) {
-    g_gather_only = true;
-    const int rc = ltmi_masks_create_csr(device, indptr, indices, data, result_dtype, n_px, n_masks, out);
-    g_gather_only = false;
-    return rc;
-}
-
-extern "C" int ltmi_masks_create_csr(int device, const int64_t *indptr, const int64_t *indices,
-                                     const void *data, int result_dtype, int64_t n_px,
-                                     int64_t n_masks, ltmi_masks **out) {
+// gather_only: the gather kernel's image alone (no blocked, scatter or banded image)
+static int create_csr(int device, const int64_t *indptr, const int64_t *indices, const void *data, int result_dtype,
+                      int64_t n_px, int64_t n_masks, ltmi_masks **out, bool gather_only) {
     if (!indptr || !out || n_px <= 0 || n_masks <= 0)
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_create_csr: bad arguments (n_px=%lld n_masks=%lld)",
                   (long long)n_px, (long long)n_masks);
@@ -834,7 +827,7 @@ extern "C" int ltmi_masks_create_csr(int device, const int64_t *indptr, const in
         const char *force = getenv("LTMI_SPARSE_BELL");
         const char *thr = getenv("LTMI_BELL_MAX_RATIO");
         const double max_ratio = thr ? atof(thr) : 8.0;
-        bool build = nnz > 0 && !c->f64 && !g_gather_only;   // (the blocked image is float32 only)
+        bool build = nnz > 0 && !c->f64 && !gather_only;   // (the blocked image is float32 only)
         if (force && force[0] == '0') build = false;
         else if (build) {
             c->bell_ratio = ltmi::bell_mac_ratio(indptr, indices, nc, n_px, n_masks);
@@ -857,7 +850,7 @@ extern "C" int ltmi_masks_create_csr(int device, const int64_t *indptr, const in
     {
         const char *force = getenv("LTMI_SPARSE_SCATTER");
         bool build = nnz > 0 && !c->f64 && n_masks * nc >= 64;
-        if (g_gather_only || (force && force[0] == '0')) build = false;
+        if (gather_only || (force && force[0] == '0')) build = false;
         else if (force && force[0] == '1') { build = nnz > 0 && !c->f64; c->scat_all = true; }
         else if (build) build = ltmi::scat_fill(indptr, indices, nc, n_px, n_masks) >= 0.15;
         if (build) {
@@ -868,7 +861,19 @@ extern "C" int ltmi_masks_create_csr(int device, const int64_t *indptr, const in
         }
     }
     c->nnz_real = (double)nnz * nc;
-    if (!c->f64 && !int_result && !g_gather_only) c->kept = ltmi::band_keep_csr(indptr, indices, vals, nc, n_px, n_masks);
+    if (!c->f64 && !int_result && !gather_only) c->kept = ltmi::band_keep_csr(indptr, indices, vals, nc, n_px, n_masks);
     *out = m;
     return LTMI_OK;
+}
+
+extern "C" int ltmi_masks_create_csr(int device, const int64_t *indptr, const int64_t *indices,
+                                     const void *data, int result_dtype, int64_t n_px,
+                                     int64_t n_masks, ltmi_masks **out) {
+    return create_csr(device, indptr, indices, data, result_dtype, n_px, n_masks, out, false);
+}
+
+extern "C" int ltmi_masks_create_csr_gather(int device, const int64_t *indptr, const int64_t *indices,
+                                            const void *data, int result_dtype, int64_t n_px,
+                                            int64_t n_masks, ltmi_masks **out) {
+    return create_csr(device, indptr, indices, data, result_dtype, n_px, n_masks, out, true);
 }

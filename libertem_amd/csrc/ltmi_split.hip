@@ -479,8 +479,7 @@ size_t split_image_bytes(const void *image) {
 }
 
 template <int NG, int TILES>
-static int launch_split(ltmi_masks *m, SplitImage *im, const float *tile, int64_t n_frames, int64_t ld,
-                        float *out, int64_t ld_out, int accumulate, hipStream_t stream) {
+static int launch_split(ltmi_masks *m, SplitImage *im, const MaskCall &call) {
     using CFG = SplitCfg<NG, TILES>;
     auto kern = k_dense_split<NG, TILES>;
     static bool attr_set[16] = {false};
@@ -489,19 +488,15 @@ static int launch_split(ltmi_masks *m, SplitImage *im, const float *tile, int64_
                                      CFG::LDS_BYTES));
         attr_set[m->device & 15] = true;
     }
-    const int64_t gx = (n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
+    const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
     const int64_t gz = im->n_gt;
     int ksplit = m->tune_ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, im->n_slots);
-    ksplit = std::max(1, std::min(ksplit, im->n_slots));
-    {
-        const int per = (im->n_slots + ksplit - 1) / ksplit;
-        ksplit = (im->n_slots + per - 1) / per;
-    }
+    ksplit = clamp_ksplit(std::max(1, std::min(ksplit, im->n_slots)), im->n_slots);
     if (ksplit > 1) {
-        const size_t need = (size_t)ksplit * n_frames * m->n_cols * sizeof(float);
+        const size_t need = (size_t)ksplit * call.n_frames * m->n_cols * sizeof(float);
         if (im->partials_bytes < need) {
-            LTMI_HIP(hipStreamSynchronize(stream));
+            LTMI_HIP(hipStreamSynchronize(call.stream));
             if (im->partials) LTMI_HIP(hipFree(im->partials));
             im->partials = nullptr;
             im->partials_bytes = 0;
@@ -510,25 +505,24 @@ static int launch_split(ltmi_masks *m, SplitImage *im, const float *tile, int64_
         }
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
-    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, stream, tile, ld, n_frames,
-                       m->n_px, (const uint16_t *)im->img, im->n_slots, out, ld_out, m->n_cols,
-                       accumulate, im->partials, ksplit);
+    hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, call.stream, (const float *)call.tile,
+                       call.ld_tile, call.n_frames, m->n_px, (const uint16_t *)im->img, im->n_slots,
+                       (float *)call.out, call.ld_out, m->n_cols, call.accumulate, im->partials, ksplit);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel),
              "k_dense_split<f,NG=%d,bf16x3,tiles=%d> grid=(%u,%u,%u)", NG, TILES, grid.x, grid.y,
              grid.z);
     if (ksplit > 1) {
-        const int64_t n = n_frames * m->n_cols;
-        hipLaunchKernelGGL(k_split_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           (const float *)im->partials, ksplit, n_frames, m->n_cols, out, ld_out,
-                           accumulate);
+        const int64_t n = call.n_frames * m->n_cols;
+        hipLaunchKernelGGL(k_split_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, call.stream,
+                           (const float *)im->partials, ksplit, call.n_frames, m->n_cols, (float *)call.out,
+                           call.ld_out, call.accumulate);
         LTMI_HIP(hipGetLastError());
     }
     return LTMI_OK;
 }
 
-int split_apply(ltmi_masks *m, void *image, const float *tile, int64_t n_frames, int64_t ld, float *out,
-                int64_t ld_out, int accumulate, hipStream_t stream) {
+int split_apply(ltmi_masks *m, void *image, const MaskCall &call) {
     SplitImage *im = (SplitImage *)image;
     // 256-frame workgroups once there are enough frames to fill the chip with them (LTMI_SPLIT_TILES
     // = 2 / 4 in the environment forces one shape: benches)
@@ -536,10 +530,8 @@ int split_apply(ltmi_masks *m, void *image, const float *tile, int64_t n_frames,
         const char *e = getenv("LTMI_SPLIT_TILES");
         return e ? atoi(e) : 0;
     }();
-    const bool big = forced ? forced == 4 : n_frames >= 2048;
-#define LTMI_SPLIT_GO(NG_)                                                                         \
-    return big ? launch_split<NG_, 4>(m, im, tile, n_frames, ld, out, ld_out, accumulate, stream)  \
-               : launch_split<NG_, 2>(m, im, tile, n_frames, ld, out, ld_out, accumulate, stream);
+    const bool big = forced ? forced == 4 : call.n_frames >= 2048;
+#define LTMI_SPLIT_GO(NG_) return big ? launch_split<NG_, 4>(m, im, call) : launch_split<NG_, 2>(m, im, call);
     if (im->ng == 4) { LTMI_SPLIT_GO(4) }
     LTMI_SPLIT_GO(2)
 #undef LTMI_SPLIT_GO
