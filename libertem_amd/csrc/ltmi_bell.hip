@@ -103,26 +103,26 @@ constexpr int BE_REC16 = 256;        // ... of a float16 record (64 lanes x 4; p
 constexpr int BE_CTL = 4;            // control words per float16 record: flags, pairs a, pairs b, -
 
 struct BellImage {
-    uint32_t *stream = nullptr;      // [blocks][64 lanes][A step 0, A step 1, pixels]
-    int64_t *stream_off = nullptr;   // [n_pass * 4 + set] first record of the stream
-    int *nblk = nullptr;             // [(active index * 4 + set) * 16 + slot] records of the pair
-    int *active = nullptr;           // [chunk][BE_NSEG] first pixel of the chunk's segments; the chunks
+    DevBuf<uint32_t> stream;         // [blocks][64 lanes][A step 0, A step 1, pixels]
+    DevBuf<int64_t> stream_off;      // [n_pass * 4 + set] first record of the stream
+    DevBuf<int> nblk;                // [(active index * 4 + set) * 16 + slot] records of the pair
+    DevBuf<int> active;              // [chunk][BE_NSEG] first pixel of the chunk's segments; the chunks
                                      // of the passes are concatenated
-    int *active_off = nullptr;       // [n_pass + 1] first chunk of a pass
+    DevBuf<int> active_off;          // [n_pass + 1] first chunk of a pass
     long crit_records = 0;           // sum over the chunks of the busiest wave's records
     bool f16 = false;                // records of 4 pixel pairs with float16 weights (k_bell_apply<.., true>)
-    float *inv_scale = nullptr;      // f16: [n_cols] 1 / power-of-two scale of the column's weights
+    DevBuf<float> inv_scale;         // f16: [n_cols] 1 / power-of-two scale of the column's weights
     BellImage *h16 = nullptr;        // the float16 image of the same stack (1- and 2-byte unsigned pixels)
     // f16 images: flat streams of k_bell_flat, one per (pass, wave)
-    uint32_t *ctrl = nullptr;        // control word per record (slot | BE_C_SKIP | BE_C_END)
-    int64_t *ctrl_off = nullptr;     // [n_pass * BE_SETS] first control word of the stream
-    int *n_rec = nullptr;            // [n_pass * BE_SETS] records of the stream (a multiple of BE_FD)
+    DevBuf<uint32_t> ctrl;           // control word per record (slot | BE_C_SKIP | BE_C_END)
+    DevBuf<int64_t> ctrl_off;        // [n_pass * BE_SETS] first control word of the stream
+    DevBuf<int> n_rec;               // [n_pass * BE_SETS] records of the stream (a multiple of BE_FD)
     int n_pass = 0;
     // entries of the last n_px % 16 pixels of a frame (at most 15): when a row is not a multiple of 16
     // bytes its last 16-byte piece is partial and is not fetched by the frame DMA; these few entries are
     // applied by k_bell_tail after the main kernel
-    int32_t *tail_px = nullptr, *tail_col = nullptr, *tail_seg = nullptr;   // sorted by column; seg: first entry of a column
-    float *tail_val = nullptr;
+    DevBuf<int32_t> tail_px, tail_col, tail_seg;   // sorted by column; seg: first entry of a column
+    DevBuf<float> tail_val;
     int n_tail = 0, n_tail_cols = 0;
     size_t n_blocks = 0;
     double mac_ratio = 0.;           // multiply-adds incl. padding / stored values
@@ -863,20 +863,7 @@ k_bell_flat(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_
 void bell_destroy(void *image) {
     BellImage *b = (BellImage *)image;
     if (!b) return;
-    if (b->stream) (void)hipFree(b->stream);
-    if (b->stream_off) (void)hipFree(b->stream_off);
-    if (b->nblk) (void)hipFree(b->nblk);
-    if (b->active) (void)hipFree(b->active);
-    if (b->active_off) (void)hipFree(b->active_off);
-    if (b->tail_px) (void)hipFree(b->tail_px);
-    if (b->tail_col) (void)hipFree(b->tail_col);
-    if (b->tail_val) (void)hipFree(b->tail_val);
-    if (b->tail_seg) (void)hipFree(b->tail_seg);
-    if (b->inv_scale) (void)hipFree(b->inv_scale);
-    if (b->ctrl) (void)hipFree(b->ctrl);
-    if (b->ctrl_off) (void)hipFree(b->ctrl_off);
-    if (b->n_rec) (void)hipFree(b->n_rec);
-    if (b->h16) bell_destroy(b->h16);
+    bell_destroy(b->h16);
     delete b;
 }
 
@@ -1302,40 +1289,30 @@ static BellImage *build_image(const int64_t *indptr, const int64_t *indices, con
         int64_t nnz = indptr[n_px] * nc;
         b->mac_ratio = nnz > 0 ? (double)(blocks - pad_blocks) * (f16 ? 256.0 : 128.0) / (double)nnz : 0.;
         if (active.empty()) active.resize(NSEG, 0);
-        hipError_t e = hipMalloc((void **)&b->stream, std::max<size_t>(stream.size(), 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->stream_off, stream_off.size() * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->nblk, nblk.size() * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->active, active.size() * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->active_off, active_off.size() * 4);
+        // (an empty stream or scale table still gets a block: the kernel's pointers are never null)
+        hipError_t e = b->stream.alloc(std::max<size_t>(stream.size(), 1));
         if (e == hipSuccess && !stream.empty())
             e = hipMemcpy(b->stream, stream.data(), stream.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->stream_off, stream_off.data(), stream_off.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->nblk, nblk.data(), nblk.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->active, active.data(), active.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->active_off, active_off.data(), active_off.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = b->stream_off.upload(stream_off.data(), stream_off.size());
+        if (e == hipSuccess) e = b->nblk.upload(nblk.data(), nblk.size());
+        if (e == hipSuccess) e = b->active.upload(active.data(), active.size());
+        if (e == hipSuccess) e = b->active_off.upload(active_off.data(), active_off.size());
         if (b->n_tail > 0) {
             const size_t nt = (size_t)b->n_tail;
-            if (e == hipSuccess) e = hipMalloc((void **)&b->tail_px, nt * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->tail_col, nt * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->tail_val, nt * 4);
-            if (e == hipSuccess) e = hipMemcpy(b->tail_px, tail_px.data(), nt * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b->tail_col, tail_col.data(), nt * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b->tail_val, tail_val.data(), nt * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->tail_seg, tail_seg.size() * 4);
-            if (e == hipSuccess) e = hipMemcpy(b->tail_seg, tail_seg.data(), tail_seg.size() * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = b->tail_px.upload(tail_px.data(), nt);
+            if (e == hipSuccess) e = b->tail_col.upload(tail_col.data(), nt);
+            if (e == hipSuccess) e = b->tail_val.upload(tail_val.data(), nt);
+            if (e == hipSuccess) e = b->tail_seg.upload(tail_seg.data(), tail_seg.size());
         }
         if (f16 && e == hipSuccess) {
-            e = hipMalloc((void **)&b->ctrl, ctrl.size() * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->ctrl_off, ctrl_off.size() * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&b->n_rec, n_rec.size() * 4);
-            if (e == hipSuccess) e = hipMemcpy(b->ctrl, ctrl.data(), ctrl.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b->ctrl_off, ctrl_off.data(), ctrl_off.size() * 8, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b->n_rec, n_rec.data(), n_rec.size() * 4, hipMemcpyHostToDevice);
+            e = b->ctrl.upload(ctrl.data(), ctrl.size());
+            if (e == hipSuccess) e = b->ctrl_off.upload(ctrl_off.data(), ctrl_off.size());
+            if (e == hipSuccess) e = b->n_rec.upload(n_rec.data(), n_rec.size());
         }
         if (f16 && e == hipSuccess) {
             std::vector<float> inv(col_scale.size());
             for (size_t k = 0; k < inv.size(); ++k) inv[k] = 1.0f / col_scale[k];
-            e = hipMalloc((void **)&b->inv_scale, std::max<size_t>(inv.size(), 1) * 4);
+            e = b->inv_scale.alloc(std::max<size_t>(inv.size(), 1));
             if (e == hipSuccess && !inv.empty())
                 e = hipMemcpy(b->inv_scale, inv.data(), inv.size() * 4, hipMemcpyHostToDevice);
         }

@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string>
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/ltmi.h"
 
@@ -103,6 +105,64 @@ static inline const char *dtype_name(int dt) {
     return (dt >= 0 && dt <= LTMI_C128) ? n[dt] : "?";
 }
 
+// One hipMalloc allocation and its owner: freed by the destructor, move-only; reads as the raw pointer it replaces
+// (kernel arguments, `if (buf)`, `buf + n`).  Counts are elements of T, bytes for DevBuf<void>.  The device of the
+// allocation must be current when the buffer goes (ltmi_masks_destroy and ltmi_fft_plan_destroy see to it).
+template <typename T>
+class DevBuf {
+    using E = typename std::conditional<std::is_void<T>::value, char, T>::type;
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t capacity() const { return cap_; }
+    size_t bytes() const { return cap_ * sizeof(E); }
+    void reset() {
+        if (p_) (void)hipFree((void *)p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // a fresh block of n elements (what the buffer held is freed first), ... zeroed, ... filled from the host
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(E));
+        if (e == hipSuccess) cap_ = n;
+        else p_ = nullptr;
+        return e;
+    }
+    hipError_t alloc_zero(size_t n) {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess ? hipMemset((void *)p_, 0, n * sizeof(E)) : e;
+    }
+    hipError_t upload(const E *host, size_t n) {
+        const hipError_t e = alloc(n);
+        return e == hipSuccess ? hipMemcpy((void *)p_, host, n * sizeof(E), hipMemcpyHostToDevice) : e;
+    }
+    // grow-only: room for n elements; a block that is too small is freed -- after the work on `stream`, which may
+    // still read it -- BEFORE the larger one is made, so a growing run never holds both.  The contents are lost.
+    int ensure(size_t n, hipStream_t stream) {
+        if (n <= cap_) return LTMI_OK;
+        if (p_) {
+            LTMI_HIP(hipStreamSynchronize(stream));
+            reset();
+        }
+        LTMI_HIP(alloc(n));
+        return LTMI_OK;
+    }
+};
+
 struct cfloat { float re, im; };
 struct cdouble { double re, im; };
 
@@ -124,7 +184,6 @@ struct MaskCall {
 struct ltmi_masks;
 namespace ltmi {
 int dense64_create(ltmi_masks *m);
-void dense64_destroy(ltmi_masks *m);
 // (img64: the handle's image or that of the shifted stack)
 int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool *handled);
 bool dense64_rows_ok(const ltmi_masks *m, const void *tile, int tile_dtype, int64_t ld);
@@ -206,7 +265,6 @@ int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, in
 // ltmi_apply_masks without the guard (ltmi_dense.hip)
 int apply_masks_unguarded(ltmi_masks *m, const MaskCall &call);
 // sparse frames against a dense stack (ltmi_csrframes.hip): the pixel-major image of the handle
-void csrframes_destroy(ltmi_masks *m);
 int bell_apply(ltmi_masks *m, void *image, int cplx, const MaskCall &call, bool *handled);
 }  // namespace ltmi
 
@@ -221,41 +279,38 @@ struct ltmi_masks {
     int n_groups = 0;        // 16-column groups, padded to a multiple of ng
     int ng = 1;
     int n_chunks = 0;
-    float *img = nullptr;
-    float *img2 = nullptr;   // slot-major image for k_dense_lds with ng > 1 (KB = 128)
+    ltmi::DevBuf<float> img;
+    ltmi::DevBuf<float> img2;   // slot-major image for k_dense_lds with ng > 1 (KB = 128)
     int n_slots2 = 0;
-    float *img3 = nullptr;   // ng3 groups + ne3 VALU columns (16 ng3 + 1..4 columns), slots of 128 px
+    ltmi::DevBuf<float> img3;   // ng3 groups + ne3 VALU columns (16 ng3 + 1..4 columns), slots of 128 px
     int n_slots3 = 0, ne3 = 0, ng3 = 0;   // ng3 full groups + ne3 VALU columns
     void *split = nullptr;   // bf16 x 3 image for float32 frames (ltmi_split.hip), stacks of >= 2 groups
     // float16 image of the standard (ng = 1) layout for unsigned 1- / 2-byte pixels (k_dense_lds X16):
     // w1 / w2 of the scaled weights in the two 16-byte units of a lane's 8 pixels; 1 / scale per column
-    float *img_h = nullptr;
-    float *img2_h = nullptr;     // ... of image 2 (ng > 1)
-    float *img3_h = nullptr;     // ... of image 3 without VALU columns (3 groups)
-    float *inv_scale = nullptr;
+    ltmi::DevBuf<float> img_h;
+    ltmi::DevBuf<float> img2_h;  // ... of image 2 (ng > 1)
+    ltmi::DevBuf<float> img3_h;  // ... of image 3 without VALU columns (3 groups)
+    ltmi::DevBuf<float> inv_scale;
     // small weights that two float16 pieces do not carry to 2^-19 relative: left out of the float16
     // images; the epilogue of k_dense_lds X16 adds their float32 products
-    int32_t *tail_px = nullptr, *tail_col = nullptr;
-    float *tail_val = nullptr;
+    ltmi::DevBuf<int32_t> tail_px, tail_col;
+    ltmi::DevBuf<float> tail_val;
     int tail_n = 0;
     // float64 results on the f64 matrix cores (ltmi_dense64.hip)
-    double *img64 = nullptr;
+    ltmi::DevBuf<double> img64;
     int n_groups64 = 0, n_chunks64 = 0;
     int cpm64 = 1;              // real columns per mask in the f64 image (2: complex128 masks)
-    void *ws64 = nullptr;
-    size_t ws64_bytes = 0;
-    void *res64 = nullptr;   // f64 scratch result of the exact-integer path
-    size_t res64_bytes = 0;
+    ltmi::DevBuf<double> ws64;    // partial sums of a K split
+    ltmi::DevBuf<double> res64;   // f64 scratch result of the exact-integer path
     int mask_bits = 64;      // integer stacks: bits needed for max |mask value|
     void *shift_cache = nullptr;   // ltmi_dense.hip: images of the stack shifted by (dy, dx)
     void *fold = nullptr;          // ltmi_fold.hip: image folded about a mirror of the detector rows (ltmi_masks_set_sig_shape)
-    float *partials = nullptr;
-    size_t partials_bytes = 0;
+    ltmi::DevBuf<void> partials;  // arrival counters, then the partial sums of a K split (ltmi_dense.hip)
     int tune_mt = 0, tune_waves = 0, tune_ksplit = 0, tune_ksplit_ring = 0;
     // kind 0 and 1
-    void *gmasks = nullptr;  // (n_masks, n_px) of the accumulate type
+    ltmi::DevBuf<void> gmasks;    // (n_masks, n_px) of the accumulate type
     // ltmi_apply_masks_csr: the stack again pixel-major, [n_px][m_pad_px] of float / double, built on first use
-    void *img_px = nullptr;
+    ltmi::DevBuf<void> img_px;
     int m_pad_px = 0;
     // kind 2 (ltmi_sparse.hip)
     void *csr = nullptr;

@@ -138,10 +138,10 @@ static int ensure_px_image(ltmi_masks *m, hipStream_t stream) {
     constexpr int V = 16 / (int)sizeof(A);
     m->m_pad_px = pad_masks(m->n_masks, V);
     const size_t n = (size_t)m->n_px * m->m_pad_px;
-    LTMI_HIP(hipMalloc(&m->img_px, n * sizeof(A)));
+    LTMI_HIP(m->img_px.alloc(n * sizeof(A)));
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 65535);
-    hipLaunchKernelGGL((k_csr_build_px<A>), dim3(blocks), dim3(256), 0, stream, (const A *)m->gmasks,
-                       (A *)m->img_px, m->n_masks, m->n_px, m->m_pad_px);
+    hipLaunchKernelGGL((k_csr_build_px<A>), dim3(blocks), dim3(256), 0, stream, (const A *)m->gmasks.get(),
+                       (A *)m->img_px.get(), m->n_masks, m->n_px, m->m_pad_px);
     LTMI_HIP(hipGetLastError());
     return LTMI_OK;
 }
@@ -154,7 +154,7 @@ static int launch_apply_csr(ltmi_masks *m, const int64_t *indptr, const int32_t 
     if (rc != LTMI_OK) return rc;
     const unsigned blocks = (unsigned)std::min<int64_t>((n_frames + 3) / 4, 1 << 20);
     hipLaunchKernelGGL((k_apply_csr<T, A>), dim3(blocks), dim3(256), 0, stream, indptr, indices, (const T *)data,
-                       rows, row0, n_frames, m->n_px, (const A *)m->img_px, m->m_pad_px, (int)m->n_masks,
+                       rows, row0, n_frames, m->n_px, (const A *)m->img_px.get(), m->m_pad_px, (int)m->n_masks,
                        (A *)out, ld_out, accumulate);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_apply_csr<%s,%s> m_pad=%d%s grid=(%u)", tname, aname,
@@ -311,11 +311,6 @@ static int launch_csr_sum_frames(const int64_t *indptr, const int32_t *indices, 
     LTMI_HIP(hipGetLastError());
     csr_sum_name("k_csr_sum_frames", tname, out_dtype, rows != nullptr);
     return LTMI_OK;
-}
-
-void csrframes_destroy(ltmi_masks *m) {
-    if (m->img_px) (void)hipFree(m->img_px);
-    m->img_px = nullptr;
 }
 
 }  // namespace ltmi

@@ -1455,8 +1455,7 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
             while (bits < 64 && (absmax >> bits) != 0) ++bits;
             m->mask_bits = bits;
         }
-        hipError_t e = hipMalloc(&m->gmasks, n * acc_size);
-        if (e == hipSuccess) e = hipMemcpy(m->gmasks, upload, n * acc_size, hipMemcpyHostToDevice);
+        const hipError_t e = m->gmasks.upload((const char *)upload, n * acc_size);
         if (e != hipSuccess) {
             ltmi_masks_destroy(m);
             LTMI_FAIL((int)e, "uploading the mask stack failed: %s", hipGetErrorString(e));
@@ -1475,13 +1474,12 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
         // interleaved (re, im) pairs) -- no host-side transform, no second upload
         const int cpm = (result_dtype == LTMI_C64) ? 2 : 1;
         const size_t n_float = (size_t)m->n_groups * m->n_chunks * CHUNK_FLOATS;
-        hipError_t e = hipMalloc((void **)&m->img, n_float * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(m->img, 0, n_float * sizeof(float));
+        hipError_t e = m->img.alloc_zero(n_float);
         if (e == hipSuccess) {
             const int64_t total = n_masks * cpm * n_px;
             const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
             hipLaunchKernelGGL(ltmi::k_build_image, dim3(blocks), dim3(256), 0, 0,
-                               (const float *)m->gmasks, m->img, n_masks, cpm, n_px, m->n_chunks);
+                               (const float *)m->gmasks.get(), m->img, n_masks, cpm, n_px, m->n_chunks);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
@@ -1490,13 +1488,12 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
             constexpr int kb = 128;
             m->n_slots2 = (int)((n_px + kb - 1) / kb);
             const size_t n2 = (size_t)m->n_groups * m->n_slots2 * GROUP * kb;
-            e = hipMalloc((void **)&m->img2, n2 * sizeof(float));
-            if (e == hipSuccess) e = hipMemset(m->img2, 0, n2 * sizeof(float));
+            e = m->img2.alloc_zero(n2);
             if (e == hipSuccess) {
                 const int64_t total = n_masks * cpm * n_px;
                 const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
                 hipLaunchKernelGGL(ltmi::k_build_image2, dim3(blocks), dim3(256), 0, 0,
-                                   (const float *)m->gmasks, m->img2, n_masks, cpm, n_px,
+                                   (const float *)m->gmasks.get(), m->img2, n_masks, cpm, n_px,
                                    m->n_slots2, m->ng, kb);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1525,13 +1522,12 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
             const int slot_floats = (m->ne3 > 0 ? ltmi::ext_slot_bytes(ng3, m->ne3)
                                                 : ng3 * GROUP * kb * 4) / 4;
             const size_t n3 = (size_t)m->n_slots3 * slot_floats;
-            e = hipMalloc((void **)&m->img3, n3 * sizeof(float));
-            if (e == hipSuccess) e = hipMemset(m->img3, 0, n3 * sizeof(float));
+            e = m->img3.alloc_zero(n3);
             if (e == hipSuccess) {
                 const int64_t total = n_masks * cpm * n_px;
                 const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
                 hipLaunchKernelGGL(ltmi::k_build_image3, dim3(blocks), dim3(256), 0, 0,
-                                   (const float *)m->gmasks, m->img3, n_masks, cpm, n_px,
+                                   (const float *)m->gmasks.get(), m->img3, n_masks, cpm, n_px,
                                    m->n_slots3, ng3, slot_floats);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1599,47 +1595,38 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
                         }
             }
             if (finite) {
-                float *scale_dev = nullptr, *amax_dev = nullptr;
-                e = hipMalloc((void **)&m->inv_scale, inv.size() * sizeof(float));
-                if (e == hipSuccess) e = hipMalloc((void **)&scale_dev, scale.size() * sizeof(float));
-                if (e == hipSuccess) e = hipMalloc((void **)&amax_dev, amax.size() * sizeof(float));
-                if (e == hipSuccess) e = hipMemcpy(amax_dev, amax.data(), amax.size() * sizeof(float), hipMemcpyHostToDevice);
+                ltmi::DevBuf<float> scale_dev, amax_dev;            // (for the image builders only)
+                e = m->inv_scale.upload(inv.data(), inv.size());
+                if (e == hipSuccess) e = scale_dev.upload(scale.data(), scale.size());
+                if (e == hipSuccess) e = amax_dev.upload(amax.data(), amax.size());
                 if (e == hipSuccess && !tail_val.empty()) {
                     const size_t nt = tail_val.size();
                     m->tail_n = (int)nt;
-                    e = hipMalloc((void **)&m->tail_px, nt * sizeof(int32_t));
-                    if (e == hipSuccess) e = hipMalloc((void **)&m->tail_col, nt * sizeof(int32_t));
-                    if (e == hipSuccess) e = hipMalloc((void **)&m->tail_val, nt * sizeof(float));
-                    if (e == hipSuccess) e = hipMemcpy(m->tail_px, tail_px.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice);
-                    if (e == hipSuccess) e = hipMemcpy(m->tail_col, tail_col.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice);
-                    if (e == hipSuccess) e = hipMemcpy(m->tail_val, tail_val.data(), nt * sizeof(float), hipMemcpyHostToDevice);
+                    e = m->tail_px.upload(tail_px.data(), nt);
+                    if (e == hipSuccess) e = m->tail_col.upload(tail_col.data(), nt);
+                    if (e == hipSuccess) e = m->tail_val.upload(tail_val.data(), nt);
                 }
-                if (e == hipSuccess) e = hipMemcpy(m->inv_scale, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice);
-                if (e == hipSuccess) e = hipMemcpy(scale_dev, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice);
                 const int64_t total = n_masks * cpm * n_px;
                 const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
-                auto build = [&](float **dst, size_t n_floats, int n_slots, int ng, int layout,
+                auto build = [&](ltmi::DevBuf<float> &dst, size_t n_floats, int n_slots, int ng, int layout,
                                  int slot_floats) {
                     if (e != hipSuccess) return;
-                    e = hipMalloc((void **)dst, n_floats * sizeof(float));
-                    if (e == hipSuccess) e = hipMemset(*dst, 0, n_floats * sizeof(float));
+                    e = dst.alloc_zero(n_floats);
                     if (e != hipSuccess) return;
                     hipLaunchKernelGGL(ltmi::k_build_image_h16, dim3(blocks), dim3(256), 0, 0,
-                                       (const float *)m->gmasks, (_Float16 *)*dst, n_masks, cpm, n_px,
+                                       (const float *)m->gmasks.get(), (_Float16 *)dst.get(), n_masks, cpm, n_px,
                                        n_slots, ng, layout, slot_floats, (const float *)scale_dev,
                                        (const float *)amax_dev);
                     e = hipGetLastError();
                 };
-                if (want_h1) build(&m->img_h, n_float, m->n_chunks, 1, 1, 0);
+                if (want_h1) build(m->img_h, n_float, m->n_chunks, 1, 1, 0);
                 if (want_h2)
-                    build(&m->img2_h, (size_t)m->n_groups * m->n_slots2 * GROUP * 128, m->n_slots2, m->ng,
+                    build(m->img2_h, (size_t)m->n_groups * m->n_slots2 * GROUP * 128, m->n_slots2, m->ng,
                           2, 0);
                 if (want_h3)
-                    build(&m->img3_h, (size_t)m->n_slots3 * (3 * GROUP * 128), m->n_slots3, 3, 3,
+                    build(m->img3_h, (size_t)m->n_slots3 * (3 * GROUP * 128), m->n_slots3, 3, 3,
                           3 * GROUP * 128);
                 if (e == hipSuccess) e = hipDeviceSynchronize();
-                if (scale_dev) (void)hipFree(scale_dev);
-                if (amax_dev) (void)hipFree(amax_dev);
             }
         }
         if (e != hipSuccess) {
@@ -1679,26 +1666,11 @@ extern "C" int ltmi_masks_destroy(ltmi_masks *m) {
     m->blocks.clear();
     (void)hipSetDevice(m->device);
     fold_destroy(m);
-    if (m->img) (void)hipFree(m->img);
-    if (m->img2) (void)hipFree(m->img2);
-    if (m->img3) (void)hipFree(m->img3);
     ltmi::split_destroy(m->split);
-    m->split = nullptr;
-    if (m->img_h) (void)hipFree(m->img_h);
-    if (m->img2_h) (void)hipFree(m->img2_h);
-    if (m->img3_h) (void)hipFree(m->img3_h);
-    if (m->inv_scale) (void)hipFree(m->inv_scale);
-    if (m->tail_px) (void)hipFree(m->tail_px);
-    if (m->tail_col) (void)hipFree(m->tail_col);
-    if (m->tail_val) (void)hipFree(m->tail_val);
-    ltmi::dense64_destroy(m);
     shift_cache_destroy(m);
-    if (m->partials) (void)hipFree(m->partials);
-    ltmi::csrframes_destroy(m);
-    if (m->gmasks) (void)hipFree(m->gmasks);
     if (m->csr) (void)ltmi::csr_destroy(m);
     ltmi::guard_destroy(m);
-    delete m;
+    delete m;                                   // (its buffers go with it)
     return LTMI_OK;
 }
 
@@ -1763,21 +1735,14 @@ extern "C" const char *ltmi_masks_last_kernel(const ltmi_masks *m) {
 constexpr size_t KCOUNT_BYTES = 64 * 1024;
 static int ensure_partials(ltmi_masks *m, size_t need, hipStream_t stream) {
     need += KCOUNT_BYTES;
-    if (need > m->partials_bytes) {
-        if (m->partials) {
-            LTMI_HIP(hipStreamSynchronize(stream));
-            LTMI_HIP(hipFree(m->partials));
-            m->partials = nullptr;
-            m->partials_bytes = 0;
-        }
-        LTMI_HIP(hipMalloc((void **)&m->partials, need));
-        LTMI_HIP(hipMemsetAsync(m->partials, 0, KCOUNT_BYTES, stream));
-        m->partials_bytes = need;
-    }
+    if (need <= m->partials.capacity()) return LTMI_OK;
+    const int rc = m->partials.ensure(need, stream);
+    if (rc != LTMI_OK) return rc;
+    LTMI_HIP(hipMemsetAsync(m->partials, 0, KCOUNT_BYTES, stream));
     return LTMI_OK;
 }
 static inline float *partial_sums(const ltmi_masks *m) {
-    return m->partials ? (float *)((char *)m->partials + KCOUNT_BYTES) : nullptr;
+    return m->partials ? (float *)((char *)m->partials.get() + KCOUNT_BYTES) : nullptr;
 }
 static inline int *partial_counters(const ltmi_masks *m, int64_t n_blocks) {
     // Off unless LTMI_KSPLIT_FUSED is set: measured on MI355X (profiles/r03_small_tiles.txt) the in-kernel
@@ -1788,7 +1753,7 @@ static inline int *partial_counters(const ltmi_masks *m, int64_t n_blocks) {
     // invalidate inside the kernel), which the kernel boundary of the second launch does once for all.
     static const bool off = getenv("LTMI_KSPLIT_FUSED") == nullptr;
     return (m->partials && !off && n_blocks * (int64_t)sizeof(int) <= (int64_t)KCOUNT_BYTES)
-               ? (int *)m->partials : nullptr;
+               ? (int *)m->partials.get() : nullptr;
 }
 
 template <typename T, int MT, int NG, int WAVES, bool ALIGNED>
@@ -2048,13 +2013,12 @@ static int launch_lds(ltmi_masks *m, const MaskCall &call) {
 // amount (built on the device from the raw stack, cached in the handle) and whole workgroups of
 // 128 frames (row lists padded with -1).  ONE launch of k_dense_lds<.., IND> for the tile.
 struct ShiftCache {
-    std::unordered_map<uint64_t, float *> images;       // key (dy, dx) -> device image
+    std::unordered_map<uint64_t, DevBuf<float>> images;       // key (dy, dx) -> device image
     bool x16 = false;                                   // the images hold float16 pieces (k_dense_lds X16)
-    size_t image_bytes = 0;
+    size_t image_bytes = 0;                             // (what the images were built for, like sig_h, sig_w and x16)
     int sig_h = 0, sig_w = 0;
-    int32_t *rows_dev = nullptr;
-    const float **wg_img_dev = nullptr;
-    size_t rows_cap = 0, wg_cap = 0;
+    DevBuf<int32_t> rows_dev;
+    DevBuf<const float *> wg_img_dev;
     // host staging of the row lists / image pointers: a small ring, so that a list is not rewritten
     // while an asynchronous copy of an earlier call may still be reading it
     static constexpr int STAGES = 4;
@@ -2063,17 +2027,14 @@ struct ShiftCache {
     int stage = 0;
     // float64 / complex128 / exact-integer results (shifted64): images in the f64 layout, scratch for
     // the frames and results of one shift group, frame numbers of the groups
-    std::unordered_map<uint64_t, double *> images64;
+    std::unordered_map<uint64_t, DevBuf<double>> images64;
     size_t image64_bytes = 0;
     int sig_h64 = 0, sig_w64 = 0;
-    void *gather = nullptr, *res = nullptr;
-    size_t gather_bytes = 0, res_bytes = 0;
-    int64_t *idx_dev = nullptr;
-    size_t idx_cap = 0;
+    DevBuf<void> gather, res;
+    DevBuf<int64_t> idx_dev;
     std::vector<int64_t> idx_stage[STAGES];
     // the shifts of the tile on the device: the per-frame kernel's, and the non-finite guard's redo
-    int32_t *shifts_dev = nullptr;
-    size_t shifts_cap = 0;
+    DevBuf<int32_t> shifts_dev;
     std::vector<int32_t> shifts_stage[STAGES];
     int shifts_stage_at = 0;                            // (a ring of its own: a call may take a stage of each)
 };
@@ -2085,17 +2046,7 @@ static uint64_t shift_key(const int32_t *shifts_host, int64_t f) {
 }
 
 static void shift_cache_destroy(ltmi_masks *m) {
-    ShiftCache *c = (ShiftCache *)m->shift_cache;
-    if (!c) return;
-    for (auto &kv : c->images) (void)hipFree(kv.second);
-    for (auto &kv : c->images64) (void)hipFree(kv.second);
-    if (c->gather) (void)hipFree(c->gather);
-    if (c->res) (void)hipFree(c->res);
-    if (c->idx_dev) (void)hipFree(c->idx_dev);
-    if (c->rows_dev) (void)hipFree(c->rows_dev);
-    if (c->shifts_dev) (void)hipFree(c->shifts_dev);
-    if (c->wg_img_dev) (void)hipFree((void *)c->wg_img_dev);
-    delete c;
+    delete (ShiftCache *)m->shift_cache;
     m->shift_cache = nullptr;
 }
 
@@ -2118,7 +2069,6 @@ static int launch_lds_shifted(ltmi_masks *m, const MaskCall &call, int sig_h, in
         x16 = m->inv_scale != nullptr && m->tail_n == 0 && !f32_instruction_only(m);   // (tail pixels would have to shift along)
     if (c->sig_h != sig_h || c->sig_w != sig_w || c->image_bytes != img_bytes || c->x16 != x16) {
         c->x16 = x16;
-        for (auto &kv : c->images) (void)hipFree(kv.second);
         c->images.clear();
         c->sig_h = sig_h;
         c->sig_w = sig_w;
@@ -2147,26 +2097,26 @@ static int launch_lds_shifted(ltmi_masks *m, const MaskCall &call, int sig_h, in
     for (uint64_t key : keys) missing += c->images.count(key) ? 0 : 1;
     if ((c->images.size() + missing) * img_bytes > SHIFT_CACHE_BYTES) {
         if (keys.size() * img_bytes > SHIFT_CACHE_BYTES) return LTMI_OK;      // not handled
-        for (auto &kv : c->images) (void)hipFree(kv.second);                  // start over
-        c->images.clear();
+        c->images.clear();                                                    // start over
     }
     const int cpm = (m->result_dtype == LTMI_C64) ? 2 : 1;
     for (uint64_t key : keys) {
         if (c->images.count(key)) continue;
-        float *img = nullptr;
-        LTMI_HIP(hipMalloc((void **)&img, img_bytes));
-        c->images.emplace(key, img);
+        DevBuf<float> fresh;
+        LTMI_HIP(fresh.alloc(img_bytes / sizeof(float)));
+        float *img = fresh;
+        c->images.emplace(key, std::move(fresh));
         LTMI_HIP(hipMemsetAsync(img, 0, img_bytes, stream));
         const int dy = (int)(int32_t)(key >> 32), dx = (int)(int32_t)(key & 0xffffffffu);
         const int64_t total = m->n_masks * cpm * m->n_px;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
         if (x16)
             hipLaunchKernelGGL(k_build_image_shifted_h16, dim3(blocks), dim3(256), 0, stream,
-                               (const float *)m->gmasks, (_Float16 *)img, m->n_masks, cpm, sig_h, sig_w,
+                               (const float *)m->gmasks.get(), (_Float16 *)img, m->n_masks, cpm, sig_h, sig_w,
                                dy, dx, m->n_chunks, (const float *)m->inv_scale);
         else
             hipLaunchKernelGGL(k_build_image_shifted, dim3(blocks), dim3(256), 0, stream,
-                               (const float *)m->gmasks, img, m->n_masks, cpm, sig_h, sig_w, dy, dx,
+                               (const float *)m->gmasks.get(), img, m->n_masks, cpm, sig_h, sig_w, dy, dx,
                                m->n_chunks);
         LTMI_HIP(hipGetLastError());
     }
@@ -2195,21 +2145,18 @@ static int launch_lds_shifted(ltmi_masks *m, const MaskCall &call, int sig_h, in
     wg_host.resize(n_wg * n_col_groups);
     for (int gi = 1; gi < n_col_groups; ++gi)
         for (size_t b = 0; b < n_wg; ++b) wg_host[gi * n_wg + b] = wg_host[b] + gi * group_floats;
-    if (c->rows_cap < rows_host.size()) {
-        if (c->rows_dev) LTMI_HIP(hipFree(c->rows_dev));
-        c->rows_dev = nullptr;
-        c->rows_cap = rows_host.size() * 2;
-        LTMI_HIP(hipMalloc((void **)&c->rows_dev, c->rows_cap * sizeof(int32_t)));
+    // (grown to twice what the tile needs: tiles of a run differ by a few workgroups)
+    if (c->rows_dev.capacity() < rows_host.size()) {
+        const int rc = c->rows_dev.ensure(rows_host.size() * 2, stream);
+        if (rc != LTMI_OK) return rc;
     }
-    if (c->wg_cap < wg_host.size()) {
-        if (c->wg_img_dev) LTMI_HIP(hipFree((void *)c->wg_img_dev));
-        c->wg_img_dev = nullptr;
-        c->wg_cap = wg_host.size() * 2;
-        LTMI_HIP(hipMalloc((void **)&c->wg_img_dev, c->wg_cap * sizeof(float *)));
+    if (c->wg_img_dev.capacity() < wg_host.size()) {
+        const int rc = c->wg_img_dev.ensure(wg_host.size() * 2, stream);
+        if (rc != LTMI_OK) return rc;
     }
     LTMI_HIP(hipMemcpyAsync(c->rows_dev, rows_host.data(), rows_host.size() * sizeof(int32_t),
                             hipMemcpyHostToDevice, stream));
-    LTMI_HIP(hipMemcpyAsync((void *)c->wg_img_dev, wg_host.data(), wg_host.size() * sizeof(float *),
+    LTMI_HIP(hipMemcpyAsync((void *)c->wg_img_dev.get(), wg_host.data(), wg_host.size() * sizeof(float *),
                             hipMemcpyHostToDevice, stream));
     auto kern = lds_kernel<T, 1, 0, 1, 0, 2>();
     if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value) {
@@ -2228,7 +2175,7 @@ static int launch_lds_shifted(ltmi_masks *m, const MaskCall &call, int sig_h, in
                            m->n_chunks, (float *)call.out + gi * GROUP, call.ld_out,
                            std::min(GROUP, m->n_cols - gi * GROUP), call.accumulate, (float *)nullptr, 1,
                            (const int32_t *)c->rows_dev,
-                           (const float *const *)c->wg_img_dev + (size_t)gi * n_wg, (int *)nullptr,
+                           (const float *const *)c->wg_img_dev.get() + (size_t)gi * n_wg, (int *)nullptr,
                            x16 ? (const float *)m->inv_scale + gi * GROUP : (const float *)nullptr,
                            (const float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr, 0);
     LTMI_HIP(hipGetLastError());
@@ -2258,7 +2205,7 @@ static int launch_mfma(ltmi_masks *m, const MaskCall &call) {
             (m->tune_ksplit_ring == 0 || m->tune_ksplit_ring == 36)) {
             if (!m->split) {
                 const int cpm = (m->result_dtype == LTMI_C64) ? 2 : 1;
-                const int rcs = ltmi::split_create(m->device, (const float *)m->gmasks, m->n_masks, cpm,
+                const int rcs = ltmi::split_create(m->device, (const float *)m->gmasks.get(), m->n_masks, cpm,
                                                    m->n_px, m->n_cols, &m->split);
                 if (rcs != LTMI_OK) return rcs;
             }
@@ -2334,7 +2281,7 @@ static int launch_generic(ltmi_masks *m, const MaskCall &call, const ShiftCtx *s
         if (shift->sel) grid.x = (unsigned)std::min<int64_t>(call.n_frames, 1024);   // (the list is short or empty)
         hipLaunchKernelGGL((k_dense_shifted<TIn, A, S>), grid, dim3(256), 0, call.stream,
                            (const TIn *)call.tile, call.ld_tile, shift->sig_h, shift->sig_w, shift->shifts,
-                           (const A *)m->gmasks, (int)m->n_masks, (S *)call.out, call.ld_out, call.accumulate,
+                           (const A *)m->gmasks.get(), (int)m->n_masks, (S *)call.out, call.ld_out, call.accumulate,
                            shift->sel, shift->n_sel);
         LTMI_HIP(hipGetLastError());
         if (shift->sel) return LTMI_OK;                   // (the route's name stays that of the product)
@@ -2343,7 +2290,7 @@ static int launch_generic(ltmi_masks *m, const MaskCall &call, const ShiftCtx *s
         return LTMI_OK;
     }
     hipLaunchKernelGGL((k_dense_generic<TIn, A, S>), grid, dim3(256), 0, call.stream, (const TIn *)call.tile,
-                       call.ld_tile, call.n_frames, m->n_px, (const A *)m->gmasks, (int)m->n_masks, (S *)call.out,
+                       call.ld_tile, call.n_frames, m->n_px, (const A *)m->gmasks.get(), (int)m->n_masks, (S *)call.out,
                        call.ld_out, call.accumulate);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_generic<%s,%s> grid=(%u,%u)",
@@ -2551,19 +2498,6 @@ __global__ void k_scatter_rows(const R *__restrict__ src, int64_t n_rows, int n_
     *p = accumulate ? (R)(*p + src[i]) : src[i];
 }
 
-static int ensure_bytes(void **buf, size_t *have, size_t need, hipStream_t stream) {
-    if (*have >= need) return LTMI_OK;
-    if (*buf) {
-        LTMI_HIP(hipStreamSynchronize(stream));
-        LTMI_HIP(hipFree(*buf));
-        *buf = nullptr;
-        *have = 0;
-    }
-    LTMI_HIP(hipMalloc(buf, need));
-    *have = need;
-    return LTMI_OK;
-}
-
 static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, const int32_t *shifts_host,
                      bool *handled) {
     *handled = false;
@@ -2599,7 +2533,6 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
     const size_t img_bytes = ltmi::dense64_image_bytes(m);
     if (c->sig_h64 != sig_h || c->sig_w64 != sig_w || c->image64_bytes != img_bytes) {
         LTMI_HIP(hipStreamSynchronize(stream));
-        for (auto &kv : c->images64) (void)hipFree(kv.second);
         c->images64.clear();
         c->sig_h64 = sig_h;
         c->sig_w64 = sig_w;
@@ -2610,14 +2543,14 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
     if ((c->images64.size() + missing) * img_bytes > SHIFT_CACHE_BYTES) {
         if (keys.size() * img_bytes > SHIFT_CACHE_BYTES) return LTMI_OK;         // not handled
         LTMI_HIP(hipStreamSynchronize(stream));
-        for (auto &kv : c->images64) (void)hipFree(kv.second);
         c->images64.clear();
     }
     for (uint64_t key : keys) {
         if (c->images64.count(key)) continue;
-        double *img = nullptr;
-        LTMI_HIP(hipMalloc((void **)&img, img_bytes));
-        c->images64.emplace(key, img);
+        DevBuf<double> fresh;
+        LTMI_HIP(fresh.alloc(img_bytes / sizeof(double)));
+        double *img = fresh;
+        c->images64.emplace(key, std::move(fresh));
         LTMI_HIP(hipMemsetAsync(img, 0, img_bytes, stream));                      // the padding
         const int rc = ltmi::dense64_build_shifted(m, sig_h, sig_w, (int)(int32_t)(key >> 32),
                                                    (int)(int32_t)(key & 0xffffffffu), img, stream);
@@ -2645,18 +2578,13 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
         largest = std::max(largest, mem.size());
         idx_host.insert(idx_host.end(), mem.begin(), mem.end());
     }
-    int rc = ensure_bytes(&c->gather, &c->gather_bytes, largest * (size_t)m->n_px * esz, stream);
+    int rc = c->gather.ensure(largest * (size_t)m->n_px * esz, stream);
     if (rc != LTMI_OK) return rc;
-    rc = ensure_bytes(&c->res, &c->res_bytes, largest * (size_t)m->n_masks * rsz, stream);
+    rc = c->res.ensure(largest * (size_t)m->n_masks * rsz, stream);
     if (rc != LTMI_OK) return rc;
-    if (c->idx_cap < idx_host.size()) {
-        if (c->idx_dev) {
-            LTMI_HIP(hipStreamSynchronize(stream));
-            LTMI_HIP(hipFree(c->idx_dev));
-        }
-        c->idx_dev = nullptr;
-        c->idx_cap = idx_host.size() * 2;
-        LTMI_HIP(hipMalloc((void **)&c->idx_dev, c->idx_cap * sizeof(int64_t)));
+    if (c->idx_dev.capacity() < idx_host.size()) {
+        rc = c->idx_dev.ensure(idx_host.size() * 2, stream);
+        if (rc != LTMI_OK) return rc;
     }
     LTMI_HIP(hipMemcpyAsync(c->idx_dev, idx_host.data(), idx_host.size() * sizeof(int64_t),
                             hipMemcpyHostToDevice, stream));
@@ -2681,14 +2609,14 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
         const int64_t ldo = ld_out * (m->result_dtype == LTMI_C128 ? 2 : 1);
         const dim3 grid((unsigned)((n * n_cols + 255) / 256));
         switch (m->result_dtype == LTMI_C128 ? 8 : (int)rsz) {
-            case 1: hipLaunchKernelGGL(k_scatter_rows<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t *)c->res, n, n_cols, idx, (uint8_t *)call.out, ldo, call.accumulate); break;
-            case 2: hipLaunchKernelGGL(k_scatter_rows<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t *)c->res, n, n_cols, idx, (uint16_t *)call.out, ldo, call.accumulate); break;
-            case 4: hipLaunchKernelGGL(k_scatter_rows<uint32_t>, grid, dim3(256), 0, stream, (const uint32_t *)c->res, n, n_cols, idx, (uint32_t *)call.out, ldo, call.accumulate); break;
+            case 1: hipLaunchKernelGGL(k_scatter_rows<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t *)c->res.get(), n, n_cols, idx, (uint8_t *)call.out, ldo, call.accumulate); break;
+            case 2: hipLaunchKernelGGL(k_scatter_rows<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t *)c->res.get(), n, n_cols, idx, (uint16_t *)call.out, ldo, call.accumulate); break;
+            case 4: hipLaunchKernelGGL(k_scatter_rows<uint32_t>, grid, dim3(256), 0, stream, (const uint32_t *)c->res.get(), n, n_cols, idx, (uint32_t *)call.out, ldo, call.accumulate); break;
             default:
                 if (m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128)
-                    hipLaunchKernelGGL(k_scatter_rows<double>, grid, dim3(256), 0, stream, (const double *)c->res, n, n_cols, idx, (double *)call.out, ldo, call.accumulate);
+                    hipLaunchKernelGGL(k_scatter_rows<double>, grid, dim3(256), 0, stream, (const double *)c->res.get(), n, n_cols, idx, (double *)call.out, ldo, call.accumulate);
                 else
-                    hipLaunchKernelGGL(k_scatter_rows<uint64_t>, grid, dim3(256), 0, stream, (const uint64_t *)c->res, n, n_cols, idx, (uint64_t *)call.out, ldo, call.accumulate);
+                    hipLaunchKernelGGL(k_scatter_rows<uint64_t>, grid, dim3(256), 0, stream, (const uint64_t *)c->res.get(), n, n_cols, idx, (uint64_t *)call.out, ldo, call.accumulate);
                 break;
         }
         LTMI_HIP(hipGetLastError());
@@ -2712,11 +2640,9 @@ static int upload_shifts(ltmi_masks *m, const int32_t *shifts_host, int64_t n_fr
         m->shift_cache = c;
     }
     const size_t need = (size_t)n_frames * 2;
-    if (c->shifts_cap < need) {
-        if (c->shifts_dev) LTMI_HIP(hipFree(c->shifts_dev));
-        c->shifts_dev = nullptr;
-        c->shifts_cap = need * 2;
-        LTMI_HIP(hipMalloc((void **)&c->shifts_dev, c->shifts_cap * sizeof(int32_t)));
+    if (c->shifts_dev.capacity() < need) {
+        const int rc = c->shifts_dev.ensure(need * 2, stream);
+        if (rc != LTMI_OK) return rc;
     }
     c->shifts_stage_at = (c->shifts_stage_at + 1) % ShiftCache::STAGES;
     std::vector<int32_t> &stage = c->shifts_stage[c->shifts_stage_at];

@@ -502,17 +502,16 @@ int dense64_create(ltmi_masks *m) {
     m->n_groups64 = (int)((m->n_masks * m->cpm64 + 15) / 16);
     m->n_chunks64 = (int)((m->n_px + KC64 - 1) / KC64);
     const size_t n = (size_t)m->n_groups64 * m->n_chunks64 * CH64;
-    LTMI_HIP(hipMalloc((void **)&m->img64, n * sizeof(double)));
-    LTMI_HIP(hipMemset(m->img64, 0, n * sizeof(double)));
+    LTMI_HIP(m->img64.alloc_zero(n));
     const int64_t total = m->n_masks * m->n_px * m->cpm64;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
     if (m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128)
         hipLaunchKernelGGL(k_build_image64<double>, dim3(blocks), dim3(256), 0, 0,
-                           (const double *)m->gmasks, m->img64, m->n_masks, m->n_px, m->n_chunks64,
+                           (const double *)m->gmasks.get(), m->img64, m->n_masks, m->n_px, m->n_chunks64,
                            m->cpm64);
     else
         hipLaunchKernelGGL(k_build_image64<int64_t>, dim3(blocks), dim3(256), 0, 0,
-                           (const int64_t *)m->gmasks, m->img64, m->n_masks, m->n_px,
+                           (const int64_t *)m->gmasks.get(), m->img64, m->n_masks, m->n_px,
                            m->n_chunks64, 1);
     LTMI_HIP(hipGetLastError());
     LTMI_HIP(hipDeviceSynchronize());
@@ -531,40 +530,17 @@ int dense64_build_shifted(ltmi_masks *m, int sig_h, int sig_w, int dy, int dx, d
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
     if (m->result_dtype == LTMI_F64 || m->result_dtype == LTMI_C128)
         hipLaunchKernelGGL(k_build_image64_shifted<double>, dim3(blocks), dim3(256), 0, stream,
-                           (const double *)m->gmasks, img, m->n_masks, m->n_px, m->n_chunks64, m->cpm64,
+                           (const double *)m->gmasks.get(), img, m->n_masks, m->n_px, m->n_chunks64, m->cpm64,
                            sig_h, sig_w, dy, dx);
     else
         hipLaunchKernelGGL(k_build_image64_shifted<int64_t>, dim3(blocks), dim3(256), 0, stream,
-                           (const int64_t *)m->gmasks, img, m->n_masks, m->n_px, m->n_chunks64, 1, sig_h,
+                           (const int64_t *)m->gmasks.get(), img, m->n_masks, m->n_px, m->n_chunks64, 1, sig_h,
                            sig_w, dy, dx);
     LTMI_HIP(hipGetLastError());
     return LTMI_OK;
 }
 
-void dense64_destroy(ltmi_masks *m) {
-    if (m->img64) (void)hipFree(m->img64);
-    if (m->ws64) (void)hipFree(m->ws64);
-    if (m->res64) (void)hipFree(m->res64);
-    m->img64 = nullptr;
-    m->ws64 = nullptr;
-    m->res64 = nullptr;
-}
-
 static inline int64_t n_cols64(const ltmi_masks *m) { return m->n_masks * m->cpm64; }
-
-static int ensure_ws64(ltmi_masks *m, size_t need, hipStream_t stream) {
-    if (m->ws64_bytes < need) {
-        if (m->ws64) {
-            LTMI_HIP(hipStreamSynchronize(stream));
-            LTMI_HIP(hipFree(m->ws64));
-            m->ws64 = nullptr;
-            m->ws64_bytes = 0;
-        }
-        LTMI_HIP(hipMalloc(&m->ws64, need));
-        m->ws64_bytes = need;
-    }
-    return LTMI_OK;
-}
 
 // at least one full mask chunk: the LDS-DMA kernel
 template <typename T>
@@ -585,20 +561,20 @@ static int launch64_lds(ltmi_masks *m, const double *img64, const MaskCall &call
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, m->n_chunks64);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks64)), m->n_chunks64);
     if (ksplit > 1) {
-        int rc = ensure_ws64(m, (size_t)ksplit * call.n_frames * n_cols64(m) * sizeof(double), call.stream);
+        const int rc = m->ws64.ensure((size_t)ksplit * call.n_frames * n_cols64(m), call.stream);
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
     hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, call.stream, tile, call.ld_tile,
                        call.n_frames, m->n_px, img64, m->n_chunks64, out, call.ld_out, (int)n_cols64(m),
-                       call.accumulate, (double *)m->ws64, ksplit, call.rows);
+                       call.accumulate, m->ws64.get(), ksplit, call.rows);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_lds64<%s%s> grid=(%u,%u,%u)",
              typeid(T).name(), call.rows ? ",rows" : "", grid.x, grid.y, grid.z);
     if (ksplit > 1) {
         const int64_t n = call.n_frames * n_cols64(m);
         hipLaunchKernelGGL(k_reduce_partials64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           call.stream, (const double *)m->ws64, ksplit, call.n_frames, (int)n_cols64(m), out,
+                           call.stream, m->ws64.get(), ksplit, call.n_frames, (int)n_cols64(m), out,
                            call.ld_out, call.accumulate);
         LTMI_HIP(hipGetLastError());
     }
@@ -655,17 +631,8 @@ static int launch64(ltmi_masks *m, const double *img64, const MaskCall &call) {
     }
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks64)), m->n_chunks64);
     if (ksplit > 1) {
-        const size_t need = (size_t)ksplit * call.n_frames * n_cols64(m) * sizeof(double);
-        if (m->ws64_bytes < need) {
-            if (m->ws64) {
-                LTMI_HIP(hipStreamSynchronize(call.stream));
-                LTMI_HIP(hipFree(m->ws64));
-                m->ws64 = nullptr;
-                m->ws64_bytes = 0;
-            }
-            LTMI_HIP(hipMalloc(&m->ws64, need));
-            m->ws64_bytes = need;
-        }
+        const int rc = m->ws64.ensure((size_t)ksplit * call.n_frames * n_cols64(m), call.stream);
+        if (rc != LTMI_OK) return rc;
     }
     const size_t lds = 2 * (size_t)CH64 * sizeof(double);          // 64 KiB
     auto kern = vec ? k_dense_mfma_f64<T, WAVES, true> : k_dense_mfma_f64<T, WAVES, false>;
@@ -674,14 +641,14 @@ static int launch64(ltmi_masks *m, const double *img64, const MaskCall &call) {
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
     hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                        img64, m->n_chunks64, out, call.ld_out, (int)n_cols64(m),
-                       call.accumulate, (double *)m->ws64, ksplit);
+                       call.accumulate, m->ws64.get(), ksplit);
     LTMI_HIP(hipGetLastError());
     snprintf(m->last_kernel, sizeof(m->last_kernel), "k_dense_mfma_f64<%s,%s> grid=(%u,%u,%u)",
              typeid(T).name(), vec ? "vec" : "guarded", grid.x, grid.y, grid.z);
     if (ksplit > 1) {
         const int64_t n = call.n_frames * n_cols64(m);
         hipLaunchKernelGGL(k_reduce_partials64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           call.stream, (const double *)m->ws64, ksplit, call.n_frames, (int)n_cols64(m), out,
+                           call.stream, m->ws64.get(), ksplit, call.n_frames, (int)n_cols64(m), out,
                            call.ld_out, call.accumulate);
         LTMI_HIP(hipGetLastError());
     }
@@ -708,17 +675,8 @@ int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool
         // product runs on the f64 matrix cores into a scratch buffer and is then truncated to the
         // result width -- bit-identical to integer arithmetic.  Otherwise: the integer VALU kernel.
         if (!int_product_is_exact(m, tile_dtype)) return LTMI_OK;
-        const size_t need = (size_t)n_frames * m->n_masks * sizeof(double);
-        if (m->res64_bytes < need) {
-            if (m->res64) {
-                LTMI_HIP(hipStreamSynchronize(stream));
-                LTMI_HIP(hipFree(m->res64));
-                m->res64 = nullptr;
-                m->res64_bytes = 0;
-            }
-            LTMI_HIP(hipMalloc(&m->res64, need));
-            m->res64_bytes = need;
-        }
+        const int rc = m->res64.ensure((size_t)n_frames * m->n_masks, stream);
+        if (rc != LTMI_OK) return rc;
         f64.out = m->res64;
         f64.ld_out = m->n_masks;
         f64.accumulate = 0;
@@ -742,7 +700,7 @@ int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool
     if (int_result) {
         const int64_t n = n_frames * m->n_masks;
         const dim3 grid((unsigned)((n + 255) / 256));
-        const double *src = (const double *)m->res64;
+        const double *src = m->res64;
         switch (dtype_size(m->result_dtype)) {
             case 1: hipLaunchKernelGGL(k_f64_to_int<uint8_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint8_t *)out, ld_out, accumulate); break;
             case 2: hipLaunchKernelGGL(k_f64_to_int<uint16_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint16_t *)out, ld_out, accumulate); break;

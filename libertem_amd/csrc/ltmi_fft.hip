@@ -17,13 +17,12 @@ struct ltmi_fft_plan {
     int batch = 0;                     // frames per hipFFT execution
     hipfftHandle plan = 0;
     bool have_plan = false;
-    float *real_buf = nullptr;         // (batch, h, w) f32
-    hipfftComplex *spec = nullptr;     // (batch, h, wc) c64
+    ltmi::DevBuf<float> real_buf;      // (batch, h, w) f32
+    ltmi::DevBuf<hipfftComplex> spec;  // (batch, h, wc) c64
     hipStream_t bound_stream = nullptr;
     bool stream_bound = false;
-    float *mask_t = nullptr;           // workspace of k_cryst_fused: both masks in lane order (ltmi_cryst.hip)
-    void *corr_ws = nullptr;           // ... of the corrections inside its row stage: dark map, patch lists / values
-    size_t corr_ws_bytes = 0;
+    ltmi::DevBuf<float> mask_t;        // workspace of k_cryst_fused: both masks in lane order (ltmi_cryst.hip)
+    ltmi::DevBuf<void> corr_ws;        // ... of the corrections inside its row stage: dark map, patch lists / values
     int n_cu = 0;
     bool fused_ok = false;             // 256 x 256 frames: k_cryst_fused (ltmi_cryst.hip) unless LTMI_FFT_FUSED=0
     char last_kernel[128] = {0};
@@ -230,11 +229,8 @@ using namespace ltmi;
 // (batch x frame) float32 workspace of a plan, created on first use
 static int real_buf_ready(ltmi_fft_plan *p) {
     if (p->real_buf) return LTMI_OK;
-    hipError_t e = hipMalloc((void **)&p->real_buf, (size_t)p->batch * p->h * p->w * sizeof(float));
-    if (e != hipSuccess) {
-        p->real_buf = nullptr;
-        LTMI_FAIL((int)e, "ltmi_fft_plan: workspace allocation failed: %s", hipGetErrorString(e));
-    }
+    const hipError_t e = p->real_buf.alloc((size_t)p->batch * p->h * p->w);
+    if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_fft_plan: workspace allocation failed: %s", hipGetErrorString(e));
     return LTMI_OK;
 }
 
@@ -242,11 +238,8 @@ static int real_buf_ready(ltmi_fft_plan *p) {
 // the 512 x 512 kernels pass from the row to the column transforms
 static int spec_ready(ltmi_fft_plan *p) {
     if (p->spec) return LTMI_OK;
-    hipError_t e = hipMalloc((void **)&p->spec, (size_t)p->batch * p->h * p->wc * sizeof(hipfftComplex));
-    if (e != hipSuccess) {
-        p->spec = nullptr;
-        LTMI_FAIL((int)e, "ltmi_fft_plan: workspace allocation failed: %s", hipGetErrorString(e));
-    }
+    const hipError_t e = p->spec.alloc((size_t)p->batch * p->h * p->wc);
+    if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_fft_plan: workspace allocation failed: %s", hipGetErrorString(e));
     return LTMI_OK;
 }
 
@@ -291,10 +284,9 @@ extern "C" int ltmi_fft_plan_create(int device, int sig_h, int sig_w, int max_ba
     if (cryst_fused_shape(sig_h, sig_w)) {
         const char *env = getenv("LTMI_FFT_FUSED");
         p->fused_ok = !(env && env[0] == '0');
-        e = hipMalloc((void **)&p->mask_t, (size_t)cryst_fused_workspace_floats(sig_h, sig_w) * sizeof(float));
+        e = p->mask_t.alloc((size_t)cryst_fused_workspace_floats(sig_h, sig_w));
         if (e == hipSuccess) e = hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, device);
         if (e != hipSuccess) {
-            if (p->mask_t) (void)hipFree(p->mask_t);
             delete p;
             LTMI_FAIL((int)e, "ltmi_fft_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
         }
@@ -304,7 +296,6 @@ extern "C" int ltmi_fft_plan_create(int device, int sig_h, int sig_w, int max_ba
     if (!p->fused_ok) {
         const int rc = hipfft_route_ready(p);
         if (rc != LTMI_OK) {
-            if (p->mask_t) (void)hipFree(p->mask_t);
             delete p;
             return rc;
         }
@@ -317,10 +308,6 @@ extern "C" int ltmi_fft_plan_destroy(ltmi_fft_plan *p) {
     if (!p) return LTMI_OK;
     (void)hipSetDevice(p->device);
     if (p->have_plan) (void)hipfftDestroy(p->plan);
-    if (p->real_buf) (void)hipFree(p->real_buf);
-    if (p->spec) (void)hipFree(p->spec);
-    if (p->corr_ws) (void)hipFree(p->corr_ws);
-    if (p->mask_t) (void)hipFree(p->mask_t);
     delete p;
     return LTMI_OK;
 }
@@ -427,16 +414,8 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
         }
         const int64_t chunk = corr.n_excl > 0 ? std::max<int64_t>(1024, ((int64_t)64 << 20) / (4 * corr.n_excl)) : n_frames;
         const size_t need = (size_t)cryst_corr_workspace_bytes(p->h, p->w, std::min(chunk, n_frames), corr.n_excl);
-        if (need > p->corr_ws_bytes) {
-            if (p->corr_ws) {
-                LTMI_HIP(hipStreamSynchronize(stream));
-                (void)hipFree(p->corr_ws);
-                p->corr_ws = nullptr;
-                p->corr_ws_bytes = 0;
-            }
-            LTMI_HIP(hipMalloc(&p->corr_ws, need));
-            p->corr_ws_bytes = need;
-        }
+        const int rcw = p->corr_ws.ensure(need, stream);
+        if (rcw != LTMI_OK) return rcw;
         bool all = true;
         for (int64_t f0 = 0; f0 < n_frames && all; f0 += chunk) {
             const int64_t n = std::min(chunk, n_frames - f0);

@@ -917,25 +917,17 @@ struct FoldImage {
     int sig_h = 0, sig_w = 0, c2 = 0;            // rows y and c2 - y are mirror partners
     int nge = 0, ngo = 0;                        // groups of even / odd columns
     int n_fold_rows = 0, n_stages = 0;
-    float *img = nullptr;
-    int2 *rows = nullptr;                        // folded row -> (y, y' or -1)
-    int *colmap = nullptr;                       // virtual column -> real column or -1
-    unsigned char *zeros = nullptr;              // 1 KiB: the partner of unpaired rows
-    size_t img_bytes = 0;
-    float *img16 = nullptr;                      // the image in 128-pixel slots (2-byte pixels), built on first use
+    ltmi::DevBuf<float> img;
+    ltmi::DevBuf<int2> rows;                     // folded row -> (y, y' or -1)
+    ltmi::DevBuf<int> colmap;                    // virtual column -> real column or -1
+    ltmi::DevBuf<unsigned char> zeros;           // 1 KiB: the partner of unpaired rows
+    ltmi::DevBuf<float> img16;                   // the image in 128-pixel slots (2-byte pixels), built on first use
     int n_stages16 = 0;
     bool img16_failed = false;
 };
 
 void ltmi::fold_destroy(ltmi_masks *m) {
-    FoldImage *f = (FoldImage *)m->fold;
-    if (!f) return;
-    if (f->img) (void)hipFree(f->img);
-    if (f->rows) (void)hipFree(f->rows);
-    if (f->colmap) (void)hipFree(f->colmap);
-    if (f->zeros) (void)hipFree(f->zeros);
-    if (f->img16) (void)hipFree(f->img16);
-    delete f;
+    delete (FoldImage *)m->fold;
     m->fold = nullptr;
 }
 
@@ -950,9 +942,9 @@ int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
     const int cpm = m->result_dtype == LTMI_C64 ? 2 : 1;
     const int groups_now = (m->n_cols + GROUP - 1) / GROUP;
     if (groups_now < 2 && !(off && atoi(off) == 2)) return LTMI_OK;     // HBM-bound already (LTMI_DENSE_FOLD=2: tests)
-    int *flags = nullptr;
+    ltmi::DevBuf<int> flags;
     const size_t nf = (size_t)2 * m->n_cols;
-    LTMI_HIP(hipMalloc((void **)&flags, nf * sizeof(int)));
+    LTMI_HIP(flags.alloc(nf));
     std::vector<int> ones(nf, 1), got(nf);
     const int64_t total = (int64_t)m->n_masks * cpm * m->n_px;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
@@ -961,13 +953,12 @@ int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
     for (int c2 : {sig_h, sig_h - 1, sig_h + 1}) {                      // centres (sig_h - 1) / 2 +- 1 / 2
         hipError_t e = hipMemcpy(flags, ones.data(), nf * sizeof(int), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(ltmi::k_fold_classify, dim3(blocks), dim3(256), 0, 0, (const float *)m->gmasks, cpm,
-                               m->n_masks, sig_h, sig_w, c2, flags, flags + m->n_cols);
+            hipLaunchKernelGGL(ltmi::k_fold_classify, dim3(blocks), dim3(256), 0, 0, (const float *)m->gmasks.get(), cpm,
+                               m->n_masks, sig_h, sig_w, c2, flags.get(), flags + m->n_cols);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpy(got.data(), flags, nf * sizeof(int), hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
-            (void)hipFree(flags);
             LTMI_FAIL((int)e, "classifying the stack's columns failed: %s", hipGetErrorString(e));
         }
         bool all = true;
@@ -979,7 +970,6 @@ int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
         }
         if (all) { best_c2 = c2; cls = c; break; }
     }
-    (void)hipFree(flags);
     if (best_c2 < 0) return LTMI_OK;
     int n_even = 0, n_odd = 0;
     for (int k = 0; k < m->n_cols; ++k) (cls[(size_t)k] > 0 ? n_even : n_odd)++;
@@ -1007,18 +997,14 @@ int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
         int ie = 0, io = nge * GROUP;
         for (int k = 0; k < m->n_cols; ++k) colmap[(size_t)(cls[(size_t)k] > 0 ? ie++ : io++)] = k;
     }
-    f->img_bytes = (size_t)f->n_stages * ltmi::fold_slot_bytes(ng);
-    hipError_t e = hipMalloc((void **)&f->img, f->img_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&f->rows, rows.size() * sizeof(int2));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->colmap, colmap.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->zeros, 1024);
-    if (e == hipSuccess) e = hipMemset(f->zeros, 0, 1024);
-    if (e == hipSuccess) e = hipMemcpy(f->rows, rows.data(), rows.size() * sizeof(int2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(f->colmap, colmap.data(), colmap.size() * sizeof(int), hipMemcpyHostToDevice);
+    hipError_t e = f->img.alloc((size_t)f->n_stages * ltmi::fold_slot_bytes(ng) / sizeof(float));
+    if (e == hipSuccess) e = f->rows.upload(rows.data(), rows.size());
+    if (e == hipSuccess) e = f->colmap.upload(colmap.data(), colmap.size());
+    if (e == hipSuccess) e = f->zeros.alloc_zero(1024);
     if (e == hipSuccess) {
         const int64_t tot = (int64_t)ng * GROUP * f->n_fold_rows * sig_w;
         const unsigned bl = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535 * 16);
-        hipLaunchKernelGGL(ltmi::k_build_fold_image, dim3(bl), dim3(256), 0, 0, (const float *)m->gmasks, f->img, cpm,
+        hipLaunchKernelGGL(ltmi::k_build_fold_image, dim3(bl), dim3(256), 0, 0, (const float *)m->gmasks.get(), f->img.get(), cpm,
                            m->n_px, sig_w, f->n_fold_rows, (const int2 *)f->rows, (const int *)f->colmap, ng);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1119,18 +1105,17 @@ bool ltmi::fold_takes16(ltmi_masks *m, const void *tile, int64_t ld, int px_byte
         const int ng = f->nge + f->ngo;
         f->n_stages16 = f->n_fold_rows * (f->sig_w / FD16_KB);
         const size_t bytes = (size_t)f->n_stages16 * ltmi::fold16_slot_bytes(ng);
-        hipError_t e = hipMalloc((void **)&f->img16, bytes);
+        hipError_t e = f->img16.alloc(bytes / sizeof(float));
         if (e == hipSuccess) {
             const int64_t tot = (int64_t)ng * GROUP * f->n_fold_rows * f->sig_w;
             const unsigned bl = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535 * 16);
-            hipLaunchKernelGGL(ltmi::k_build_fold_image16, dim3(bl), dim3(256), 0, 0, (const float *)m->gmasks, f->img16,
+            hipLaunchKernelGGL(ltmi::k_build_fold_image16, dim3(bl), dim3(256), 0, 0, (const float *)m->gmasks.get(), f->img16.get(),
                                cpm, m->n_px, f->sig_w, f->n_fold_rows, (const int2 *)f->rows, (const int *)f->colmap, ng);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
         if (e != hipSuccess) {
-            if (f->img16) (void)hipFree(f->img16);
-            f->img16 = nullptr;
+            f->img16.reset();
             f->img16_failed = true;
             (void)hipGetLastError();
             return false;
@@ -1211,19 +1196,19 @@ struct ltmi::KeptCsr {
 struct BandImage {
     int sig_h = 0, sig_w = 0, c2 = 0, nge = 0, ngo = 0;
     int n_blocks = 0, n_stages = 0, n_fold_rows = 0;
-    float *img = nullptr;
-    int4 *stages = nullptr;
-    int *blk_off = nullptr, *colmap = nullptr;
-    unsigned char *zeros = nullptr;
+    ltmi::DevBuf<float> img;
+    ltmi::DevBuf<int4> stages;
+    ltmi::DevBuf<int> blk_off, colmap;
+    ltmi::DevBuf<unsigned char> zeros;
     double reread = 0.;                         // stages per stage of the whole detector: how often a frame byte is read
     // 1- / 2-byte integer frames: 128-pixel stages (k_dense_fold16); the lists are made with the float32 image, the
     // image itself on the first integer tile (k_build_band_image16)
     std::vector<int4> stages16_host;
     std::vector<int4> src16_host;                // two per stage: the 64-pixel stages it is made of, their first pixels
     std::vector<int> blk_off16_host;
-    float *img16 = nullptr;
-    int4 *stages16 = nullptr;
-    int *blk_off16 = nullptr;
+    ltmi::DevBuf<float> img16;
+    ltmi::DevBuf<int4> stages16;
+    ltmi::DevBuf<int> blk_off16;
     int n_stages16 = 0;
     bool img16_failed = false;
     double reread16 = 0.;
@@ -1272,19 +1257,7 @@ ltmi::KeptCsr *ltmi::band_keep_csr(const int64_t *indptr, const int64_t *indices
 
 void ltmi::band_free_csr(KeptCsr *k) { delete k; }
 
-void ltmi::band_destroy(void *band) {
-    BandImage *b = (BandImage *)band;
-    if (!b) return;
-    if (b->img) (void)hipFree(b->img);
-    if (b->stages) (void)hipFree(b->stages);
-    if (b->blk_off) (void)hipFree(b->blk_off);
-    if (b->colmap) (void)hipFree(b->colmap);
-    if (b->zeros) (void)hipFree(b->zeros);
-    if (b->img16) (void)hipFree(b->img16);
-    if (b->stages16) (void)hipFree(b->stages16);
-    if (b->blk_off16) (void)hipFree(b->blk_off16);
-    delete b;
-}
+void ltmi::band_destroy(void *band) { delete (BandImage *)band; }
 
 // `other_macs`: padded multiply-adds per frame of the kernel that would run instead (blocked image), 0: unknown.
 // Returns the image or nullptr (no mirror, no common supports, not worth it, no memory: the other kernels serve).
@@ -1598,16 +1571,11 @@ void *ltmi::band_build(const KeptCsr *k, int sig_h, int sig_w, double other_macs
         bi->blk_off16_host.swap(blk_off16);
         bi->n_stages16 = (int)bi->stages16_host.size();
         bi->reread16 = with16 ? (double)bi->n_stages16 / (double)(rows.size() * (size_t)(sig_w / FD16_KB)) : 0.;
-        hipError_t e = hipMalloc((void **)&bi->img, img.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **)&bi->stages, stages.size() * sizeof(int4));
-        if (e == hipSuccess) e = hipMalloc((void **)&bi->blk_off, blk_off.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&bi->colmap, colmap.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&bi->zeros, 1024);
-        if (e == hipSuccess) e = hipMemset(bi->zeros, 0, 1024);
-        if (e == hipSuccess) e = hipMemcpy(bi->img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(bi->stages, stages.data(), stages.size() * sizeof(int4), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(bi->blk_off, blk_off.data(), blk_off.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(bi->colmap, colmap.data(), colmap.size() * sizeof(int), hipMemcpyHostToDevice);
+        hipError_t e = bi->img.upload(img.data(), img.size());
+        if (e == hipSuccess) e = bi->stages.upload(stages.data(), stages.size());
+        if (e == hipSuccess) e = bi->blk_off.upload(blk_off.data(), blk_off.size());
+        if (e == hipSuccess) e = bi->colmap.upload(colmap.data(), colmap.size());
+        if (e == hipSuccess) e = bi->zeros.alloc_zero(1024);
         if (e != hipSuccess) {
             band_destroy(bi);
             (void)hipGetLastError();
@@ -1631,35 +1599,23 @@ bool ltmi::band_takes(void *band, const ltmi_masks *m, const void *tile, int til
     if (!b->img16) {
         // first integer tile: the image in 128-pixel slots from the float32 one
         const int ng = b->nge + b->ngo;
-        int4 *src = nullptr;
-        hipError_t e = hipMalloc((void **)&b->img16, (size_t)b->n_stages16 * ltmi::fold16_slot_bytes(ng));
-        if (e == hipSuccess) e = hipMalloc((void **)&b->stages16, b->stages16_host.size() * sizeof(int4));
-        if (e == hipSuccess) e = hipMalloc((void **)&b->blk_off16, b->blk_off16_host.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&src, b->src16_host.size() * sizeof(int4));
-        if (e == hipSuccess)
-            e = hipMemcpy(b->stages16, b->stages16_host.data(), b->stages16_host.size() * sizeof(int4),
-                          hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(b->blk_off16, b->blk_off16_host.data(), b->blk_off16_host.size() * sizeof(int),
-                          hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(src, b->src16_host.data(), b->src16_host.size() * sizeof(int4), hipMemcpyHostToDevice);
+        ltmi::DevBuf<int4> src;                                        // (for the builder only)
+        hipError_t e = b->img16.alloc((size_t)b->n_stages16 * ltmi::fold16_slot_bytes(ng) / sizeof(float));
+        if (e == hipSuccess) e = b->stages16.upload(b->stages16_host.data(), b->stages16_host.size());
+        if (e == hipSuccess) e = b->blk_off16.upload(b->blk_off16_host.data(), b->blk_off16_host.size());
+        if (e == hipSuccess) e = src.upload(b->src16_host.data(), b->src16_host.size());
         if (e == hipSuccess) {
             const int64_t tot = (int64_t)b->n_stages16 * ng * GROUP * FD16_KB;
             const unsigned bl = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535 * 16);
-            hipLaunchKernelGGL(ltmi::k_build_band_image16, dim3(bl), dim3(256), 0, 0, (const float *)b->img, b->img16,
+            hipLaunchKernelGGL(ltmi::k_build_band_image16, dim3(bl), dim3(256), 0, 0, (const float *)b->img, b->img16.get(),
                                (const int4 *)b->stages16, (const int4 *)src, ng, (int64_t)b->n_stages16);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
-        if (src) (void)hipFree(src);
         if (e != hipSuccess) {
-            if (b->img16) (void)hipFree(b->img16);
-            if (b->stages16) (void)hipFree(b->stages16);
-            if (b->blk_off16) (void)hipFree(b->blk_off16);
-            b->img16 = nullptr;
-            b->stages16 = nullptr;
-            b->blk_off16 = nullptr;
+            b->img16.reset();
+            b->stages16.reset();
+            b->blk_off16.reset();
             b->img16_failed = true;
             (void)hipGetLastError();
             return false;

@@ -31,11 +31,9 @@ namespace ltmi {
 bool csr_has_fast_image(const ltmi_masks *m);      // ltmi_sparse.hip
 
 struct NfGuard {
-    int *ctl = nullptr;          // [0] = number of listed frames, [1 .. 1 + cap) = per-frame "listed" flags
-    int32_t *list = nullptr;     // listed frames (result rows)
-    int64_t cap = 0;
-    void *scratch = nullptr;     // accumulate != 0 / `out` in host memory: the product lands here first
-    size_t scratch_bytes = 0;
+    DevBuf<int> ctl;             // [0] = number of listed frames, [1 .. 1 + frames) = per-frame "listed" flags
+    DevBuf<int32_t> list;        // listed frames (result rows)
+    DevBuf<void> scratch;        // accumulate != 0 / `out` in host memory: the product lands here first
     const void *last_out = nullptr;   // (one-entry cache of out_is_host)
     bool last_out_host = false;
     bool last_checked = false;        // the last guarded product went through k_flag_rows (ltmi_masks_nonfinite_frames)
@@ -43,9 +41,9 @@ struct NfGuard {
 };
 
 struct DenseOrigin {
-    int32_t *indptr = nullptr;   // (n_px + 1) CSR over pixels
-    int32_t *indices = nullptr;  // (nnz) mask index
-    int32_t *unstored = nullptr; // pixels no mask stores
+    DevBuf<int32_t> indptr;      // (n_px + 1) CSR over pixels
+    DevBuf<int32_t> indices;     // (nnz) mask index
+    DevBuf<int32_t> unstored;    // pixels no mask stores
     int64_t n_unstored = 0;
 };
 
@@ -173,13 +171,8 @@ bool guard_wanted(const ltmi_masks *m, int tile_dtype) {
 }
 
 static void dense_origin_free(ltmi_masks *m) {
-    if (DenseOrigin *d = (DenseOrigin *)m->dense_origin) {
-        if (d->indptr) (void)hipFree(d->indptr);
-        if (d->indices) (void)hipFree(d->indices);
-        if (d->unstored) (void)hipFree(d->unstored);
-        delete d;
-        m->dense_origin = nullptr;
-    }
+    delete (DenseOrigin *)m->dense_origin;
+    m->dense_origin = nullptr;
 }
 
 // a product that bypasses the guard (integer frames, guard switched off): ltmi_masks_nonfinite_frames reports 0 for it
@@ -193,13 +186,8 @@ void guard_destroy(ltmi_masks *m) {
         m->sparse_origin = nullptr;
     }
     dense_origin_free(m);
-    if (NfGuard *g = (NfGuard *)m->guard) {
-        if (g->ctl) (void)hipFree(g->ctl);
-        if (g->list) (void)hipFree(g->list);
-        if (g->scratch) (void)hipFree(g->scratch);
-        delete g;
-        m->guard = nullptr;
-    }
+    delete (NfGuard *)m->guard;
+    m->guard = nullptr;
 }
 
 static int guard_ensure(ltmi_masks *m, int64_t n_frames, size_t scratch_bytes, hipStream_t stream, NfGuard **out) {
@@ -209,31 +197,11 @@ static int guard_ensure(ltmi_masks *m, int64_t n_frames, size_t scratch_bytes, h
         if (!g) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
         m->guard = g;
     }
-    if (g->cap < n_frames) {
-        if (g->ctl) {
-            LTMI_HIP(hipStreamSynchronize(stream));       // (a launch in flight may still read the old lists)
-            (void)hipFree(g->ctl);
-            (void)hipFree(g->list);
-            g->ctl = nullptr;
-            g->list = nullptr;
-            g->cap = 0;
-        }
-        LTMI_HIP(hipMalloc((void **)&g->ctl, (size_t)(n_frames + 1) * sizeof(int)));
-        LTMI_HIP(hipMalloc((void **)&g->list, (size_t)n_frames * sizeof(int32_t)));
-        g->cap = n_frames;
-    }
-    if (g->scratch_bytes < scratch_bytes) {
-        if (g->scratch) {
-            LTMI_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(g->scratch);
-            g->scratch = nullptr;
-            g->scratch_bytes = 0;
-        }
-        LTMI_HIP(hipMalloc(&g->scratch, scratch_bytes));
-        g->scratch_bytes = scratch_bytes;
-    }
+    int rc = g->ctl.ensure((size_t)n_frames + 1, stream);       // (a launch in flight may still read the old lists)
+    if (rc == LTMI_OK) rc = g->list.ensure((size_t)n_frames, stream);
+    if (rc == LTMI_OK) rc = g->scratch.ensure(scratch_bytes, stream);
     *out = g;
-    return LTMI_OK;
+    return rc;
 }
 
 // Where a guarded product lands: `out` itself, or the device scratch ((n_frames, n_masks), written, not added to).
@@ -251,7 +219,7 @@ int guard_target(ltmi_masks *m, int64_t n_frames, void *out, int64_t ld_out, int
         rc = guard_ensure(m, n_frames, (size_t)n_frames * m->n_masks * elem, stream, &g);
         if (rc != LTMI_OK) return rc;
     }
-    *target = g->via_scratch ? g->scratch : out;
+    *target = g->via_scratch ? g->scratch.get() : out;
     *ld_target = g->via_scratch ? m->n_masks : ld_out;
     return LTMI_OK;
 }
@@ -290,7 +258,7 @@ int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, in
         const int words = (int)(m->n_masks * elem / 4);
         const int64_t total = n_frames * words;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_guard_copy_rows, dim3(blocks), dim3(256), 0, stream, (const uint32_t *)g->scratch,
+        hipLaunchKernelGGL(k_guard_copy_rows, dim3(blocks), dim3(256), 0, stream, (const uint32_t *)g->scratch.get(),
                            (int64_t)words, (uint32_t *)out, ld_out * (int64_t)elem / 4, n_frames, words);
         LTMI_HIP(hipGetLastError());
     }
@@ -417,13 +385,9 @@ extern "C" int ltmi_masks_set_dense_origin(ltmi_masks *m, const int64_t *indptr,
     }
     for (int64_t p = 0; p < m->n_px; ++p)
         if (indptr[p + 1] == indptr[p]) un.push_back((int32_t)p);
-    hipError_t e = hipMalloc((void **)&d->indptr, ip.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d->indices, ix.size() * sizeof(int32_t));
-    if (e == hipSuccess && !un.empty()) e = hipMalloc((void **)&d->unstored, un.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(d->indptr, ip.data(), ip.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d->indices, ix.data(), ix.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !un.empty())
-        e = hipMemcpy(d->unstored, un.data(), un.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    hipError_t e = d->indptr.upload(ip.data(), ip.size());
+    if (e == hipSuccess) e = d->indices.upload(ix.data(), ix.size());
+    if (e == hipSuccess && !un.empty()) e = d->unstored.upload(un.data(), un.size());
     d->n_unstored = (int64_t)un.size();
     dense_origin_free(m);
     m->dense_origin = d;

@@ -67,15 +67,15 @@ static_assert(SCAT_PITCH == SC_ROW + 4 && SCAT_BUF == SC_FB * SCAT_PITCH && SCAT
 
 struct ScatImage {                       // the image of a stack for ONE pixel size
     int sz = 0, n_pass = 0;
-    uint32_t *hdr = nullptr;             // 4 words per block
-    float *wts = nullptr;                // 32 weights per block
-    int64_t *stream_off = nullptr;       // [n_pass * 16 + 1] first block of a wave's stream
-    int32_t *n_blk = nullptr;            // [n_pass * 16] blocks of the stream (incl. the leading dummy)
-    int32_t *dma_off = nullptr;          // [chunks of all passes][64] byte offset in the frame row
-    int32_t *active_off = nullptr;       // [n_pass + 1]
-    int32_t *col_of_slot = nullptr;      // [n_pass * 16 * 64] column of an accumulator slot, -1: none
-    int32_t *tail_px = nullptr, *tail_col = nullptr;   // entries of pixels behind the last full 16-byte piece
-    float *tail_val = nullptr;
+    DevBuf<uint32_t> hdr;                // 4 words per block
+    DevBuf<float> wts;                   // 32 weights per block
+    DevBuf<int64_t> stream_off;          // [n_pass * 16 + 1] first block of a wave's stream
+    DevBuf<int32_t> n_blk;               // [n_pass * 16] blocks of the stream (incl. the leading dummy)
+    DevBuf<int32_t> dma_off;             // [chunks of all passes][64] byte offset in the frame row
+    DevBuf<int32_t> active_off;          // [n_pass + 1]
+    DevBuf<int32_t> col_of_slot;         // [n_pass * 16 * 64] column of an accumulator slot, -1: none
+    DevBuf<int32_t> tail_px, tail_col;   // entries of pixels behind the last full 16-byte piece
+    DevBuf<float> tail_val;
     int n_tail = 0;
     size_t n_blocks = 0, n_bundles = 0;
     long crit_blocks = 0;                // sum over chunks of the busiest wave's blocks
@@ -91,19 +91,10 @@ struct ScatSet {                         // host copy of the CSR matrix + the im
     bool failed[3] = {false, false, false};
 };
 
-static void image_destroy(ScatImage *b) {
-    if (!b) return;
-    void *p[] = {b->hdr, b->wts, b->stream_off, b->n_blk, b->dma_off, b->active_off, b->col_of_slot,
-                 b->tail_px, b->tail_col, b->tail_val};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    delete b;
-}
-
 void scat_destroy(void *set) {
     ScatSet *s = (ScatSet *)set;
     if (!s) return;
-    for (ScatImage *b : s->img) image_destroy(b);
+    for (ScatImage *b : s->img) delete b;
     delete s;
 }
 
@@ -324,10 +315,11 @@ struct Bundle {
     float w[8];
 };
 
-template <typename V> static hipError_t upload(V **dst, const std::vector<V> &src) {
-    hipError_t e = hipMalloc((void **)dst, std::max<size_t>(src.size(), 1) * sizeof(V));
+// (an empty table still gets a block: the kernel's pointers are never null)
+template <typename V> static hipError_t upload(DevBuf<V> &dst, const std::vector<V> &src) {
+    hipError_t e = dst.alloc(std::max<size_t>(src.size(), 1));
     if (e == hipSuccess && !src.empty())
-        e = hipMemcpy(*dst, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice);
+        e = hipMemcpy(dst, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice);
     return e;
 }
 
@@ -532,26 +524,26 @@ static ScatImage *build_image(const ScatSet &s, int sz, int *err) {
         stream_off.back() = (int64_t)(hdr.size() / 4);
         if (dma_off.empty()) dma_off.assign(64, 0);
         b->fill = b->n_bundles ? (double)stored / (8.0 * (double)b->n_bundles) : 0.0;
-        hipError_t e = upload(&b->hdr, hdr);
-        if (e == hipSuccess) e = upload(&b->wts, wts);
-        if (e == hipSuccess) e = upload(&b->stream_off, stream_off);
-        if (e == hipSuccess) e = upload(&b->n_blk, n_blk);
-        if (e == hipSuccess) e = upload(&b->dma_off, dma_off);
-        if (e == hipSuccess) e = upload(&b->active_off, active_off);
-        if (e == hipSuccess) e = upload(&b->col_of_slot, col_of_slot);
-        if (e == hipSuccess && b->n_tail) e = upload(&b->tail_px, tail_px);
-        if (e == hipSuccess && b->n_tail) e = upload(&b->tail_col, tail_col);
-        if (e == hipSuccess && b->n_tail) e = upload(&b->tail_val, tail_val);
+        hipError_t e = upload(b->hdr, hdr);
+        if (e == hipSuccess) e = upload(b->wts, wts);
+        if (e == hipSuccess) e = upload(b->stream_off, stream_off);
+        if (e == hipSuccess) e = upload(b->n_blk, n_blk);
+        if (e == hipSuccess) e = upload(b->dma_off, dma_off);
+        if (e == hipSuccess) e = upload(b->active_off, active_off);
+        if (e == hipSuccess) e = upload(b->col_of_slot, col_of_slot);
+        if (e == hipSuccess && b->n_tail) e = upload(b->tail_px, tail_px);
+        if (e == hipSuccess && b->n_tail) e = upload(b->tail_col, tail_col);
+        if (e == hipSuccess && b->n_tail) e = upload(b->tail_val, tail_val);
         if (e != hipSuccess) {
             set_error("uploading the scatter image failed: %s", hipGetErrorString(e));
             *err = (int)e;
-            image_destroy(b);
+            delete b;
             return nullptr;
         }
     } catch (const std::bad_alloc &) {
         set_error("out of host memory while packing the scatter image of a sparse stack");
         *err = LTMI_E_NOMEM;
-        image_destroy(b);
+        delete b;
         return nullptr;
     }
     return b;

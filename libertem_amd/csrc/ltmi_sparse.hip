@@ -47,12 +47,12 @@ struct CsrImage {
     int mb = 1024;              // masks per pass = 256 * mpt
     int n_pass = 0;
     int n_chunks = 0;
-    uint32_t *pix = nullptr;    // [rows][64]
-    float *val = nullptr;       // [rows][64] (x2 interleaved re/im for complex)
-    double *val64 = nullptr;    // float64 results: the values as doubles instead (f64 != 0)
+    DevBuf<uint32_t> pix;       // [rows][64]
+    DevBuf<float> val;          // [rows][64] (x2 interleaved re/im for complex)
+    DevBuf<double> val64;       // float64 results: the values as doubles instead (f64 != 0)
     int f64 = 0;
-    int *row_off = nullptr;     // [(pass * n_chunks + chunk) * mpt * 4 + slot * 4 + wave]
-    int *row_len = nullptr;
+    DevBuf<int> row_off;        // [(pass * n_chunks + chunk) * mpt * 4 + slot * 4 + wave]
+    DevBuf<int> row_len;
     size_t n_rows = 0;
     void *scat = nullptr;       // ltmi_scatter.hip: the stack for k_scatter (images built per pixel size on first use)
     bool scat_all = false;      // LTMI_SPARSE_SCATTER=1: k_scatter for every pixel type (default: float32 frames)
@@ -60,8 +60,8 @@ struct CsrImage {
     KeptCsr *kept = nullptr;    // host copy until the detector shape is known (ltmi_masks_set_sig_shape) or the first product
     void *band = nullptr;       // ltmi_fold.hip: column blocks with a common support each, folded (float32 frames)
     double nnz_real = 0.;
-    int *active = nullptr;      // chunks with entries, concatenated per pass
-    int *active_off = nullptr;  // [n_pass + 1]
+    DevBuf<int> active;         // chunks with entries, concatenated per pass
+    DevBuf<int> active_off;     // [n_pass + 1]
     void *bell = nullptr;       // blocked image for the matrix-core kernel (ltmi_bell.hip) or null
     // integer result dtypes: the values are held as doubles (f64 = 1) and a product whose every
     // partial sum stays below 2^52 is exact in the float64 gather kernel (see csr_apply)
@@ -321,13 +321,6 @@ namespace ltmi {
 int csr_destroy(ltmi_masks *m) {
     CsrImage *c = (CsrImage *)m->csr;
     if (!c) return LTMI_OK;
-    if (c->pix) (void)hipFree(c->pix);
-    if (c->val) (void)hipFree(c->val);
-    if (c->val64) (void)hipFree(c->val64);
-    if (c->row_off) (void)hipFree(c->row_off);
-    if (c->row_len) (void)hipFree(c->row_len);
-    if (c->active) (void)hipFree(c->active);
-    if (c->active_off) (void)hipFree(c->active_off);
     bell_destroy(c->bell);
     scat_destroy(c->scat);
     band_destroy(c->band);
@@ -561,17 +554,8 @@ int csr_apply(ltmi_masks *m, const MaskCall &call) {
         if (!csr_int_exact(m, tile_dtype))
             LTMI_FAIL(LTMI_E_DTYPE, "sparse integer masks: %s tiles against this stack can exceed 2^52 "
                       "(densify the stack: the integer VALU kernel)", dtype_name(tile_dtype));
-        const size_t need = (size_t)n_frames * m->n_masks * sizeof(double);
-        if (m->res64_bytes < need) {
-            if (m->res64) {
-                LTMI_HIP(hipStreamSynchronize(stream));
-                LTMI_HIP(hipFree(m->res64));
-                m->res64 = nullptr;
-                m->res64_bytes = 0;
-            }
-            LTMI_HIP(hipMalloc(&m->res64, need));
-            m->res64_bytes = need;
-        }
+        const int rc64 = m->res64.ensure((size_t)n_frames * m->n_masks, stream);
+        if (rc64 != LTMI_OK) return rc64;
         MaskCall sums = call;
         sums.out = m->res64;
         sums.ld_out = m->n_masks;
@@ -580,7 +564,7 @@ int csr_apply(ltmi_masks *m, const MaskCall &call) {
         if (rc != LTMI_OK) return rc;
         const int64_t n = n_frames * m->n_masks;
         const dim3 grid((unsigned)((n + 255) / 256));
-        const double *src = (const double *)m->res64;
+        const double *src = m->res64;
         switch (dtype_size(m->result_dtype)) {
             case 1: hipLaunchKernelGGL(k_sell_f64_to_int<uint8_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint8_t *)out, ld_out, accumulate); break;
             case 2: hipLaunchKernelGGL(k_sell_f64_to_int<uint16_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint16_t *)out, ld_out, accumulate); break;
@@ -796,20 +780,13 @@ static int create_csr(int device, const int64_t *indptr, const int64_t *indices,
             }
         }
         const size_t n_slices_dev = n_tab;
-        hipError_t e = hipMalloc((void **)&c->pix, pix.size() * sizeof(uint32_t));
-        if (e == hipSuccess && !c->f64) e = hipMalloc((void **)&c->val, val.size() * sizeof(float));
-        if (e == hipSuccess && c->f64) e = hipMalloc((void **)&c->val64, val64.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->row_off, n_slices_dev * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->row_len, n_slices_dev * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->active, active.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&c->active_off, active_off.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpy(c->active, active.data(), active.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(c->active_off, active_off.data(), active_off.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(c->pix, pix.data(), pix.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !c->f64) e = hipMemcpy(c->val, val.data(), val.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess && c->f64) e = hipMemcpy(c->val64, val64.data(), val64.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(c->row_off, row_off.data(), n_slices_dev * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(c->row_len, row_len.data(), n_slices_dev * sizeof(int), hipMemcpyHostToDevice);
+        hipError_t e = c->pix.upload(pix.data(), pix.size());
+        if (e == hipSuccess && !c->f64) e = c->val.upload(val.data(), val.size());
+        if (e == hipSuccess && c->f64) e = c->val64.upload(val64.data(), val64.size());
+        if (e == hipSuccess) e = c->row_off.upload(row_off.data(), n_slices_dev);
+        if (e == hipSuccess) e = c->row_len.upload(row_len.data(), n_slices_dev);
+        if (e == hipSuccess) e = c->active.upload(active.data(), active.size());
+        if (e == hipSuccess) e = c->active_off.upload(active_off.data(), active_off.size());
         if (e != hipSuccess) {
             ltmi::csr_destroy(m);
             delete m;

@@ -52,10 +52,9 @@ constexpr int SP_WAVES = 4;
 // image: [group tile gt][slot][group g of NG][plane 3][unit u = px / 8][column n 16][8 bf16]
 //   -> a wave's B fragment read (lane (n, kg) reads unit blk * 4 + kg) is 1 KiB contiguous
 struct SplitImage {
-    uint16_t *img = nullptr;
+    DevBuf<uint16_t> img;
     int ng = 0, kb = 0, n_slots = 0, n_gt = 0;
-    float *partials = nullptr;
-    size_t partials_bytes = 0;
+    DevBuf<float> partials;
 };
 
 __device__ __forceinline__ uint16_t bf16_rn(float v) {           // round to nearest even, finite input
@@ -446,8 +445,7 @@ int split_create(int device, const float *gmasks, int64_t n_masks, int cpm, int6
     im->n_slots = (int)(n_px / im->kb);
     im->n_gt = (n_groups + im->ng - 1) / im->ng;
     const size_t bytes = (size_t)im->n_gt * im->n_slots * SP_BSLOT;
-    hipError_t e = hipMalloc((void **)&im->img, bytes);
-    if (e == hipSuccess) e = hipMemset(im->img, 0, bytes);
+    hipError_t e = im->img.alloc_zero(bytes / sizeof(uint16_t));
     if (e == hipSuccess) {
         const int64_t total = n_masks * cpm * n_px;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16);
@@ -457,7 +455,6 @@ int split_create(int device, const float *gmasks, int64_t n_masks, int cpm, int6
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess) {
-        if (im->img) (void)hipFree(im->img);
         delete im;
         LTMI_FAIL((int)e, "building the split mask image failed: %s", hipGetErrorString(e));
     }
@@ -465,13 +462,7 @@ int split_create(int device, const float *gmasks, int64_t n_masks, int cpm, int6
     return LTMI_OK;
 }
 
-void split_destroy(void *image) {
-    SplitImage *im = (SplitImage *)image;
-    if (!im) return;
-    if (im->img) (void)hipFree(im->img);
-    if (im->partials) (void)hipFree(im->partials);
-    delete im;
-}
+void split_destroy(void *image) { delete (SplitImage *)image; }
 
 size_t split_image_bytes(const void *image) {
     const SplitImage *im = (const SplitImage *)image;
@@ -494,15 +485,8 @@ static int launch_split(ltmi_masks *m, SplitImage *im, const MaskCall &call) {
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, im->n_slots);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, im->n_slots)), im->n_slots);
     if (ksplit > 1) {
-        const size_t need = (size_t)ksplit * call.n_frames * m->n_cols * sizeof(float);
-        if (im->partials_bytes < need) {
-            LTMI_HIP(hipStreamSynchronize(call.stream));
-            if (im->partials) LTMI_HIP(hipFree(im->partials));
-            im->partials = nullptr;
-            im->partials_bytes = 0;
-            LTMI_HIP(hipMalloc((void **)&im->partials, need));
-            im->partials_bytes = need;
-        }
+        const int rc = im->partials.ensure((size_t)ksplit * call.n_frames * m->n_cols, call.stream);
+        if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit, (unsigned)gz);
     hipLaunchKernelGGL(kern, grid, dim3(CFG::WAVES * 64), CFG::LDS_BYTES, call.stream, (const float *)call.tile,
