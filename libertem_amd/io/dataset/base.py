@@ -483,6 +483,17 @@ class DataSet:
     def check_valid(self):
         return True
 
+    @classmethod
+    def get_supported_extensions(cls):
+        """file extensions (lower case, no dot) that bring this type to the front of the detection order"""
+        return set()
+
+    @classmethod
+    def detect_params(cls, path, executor=None):
+        """-> {'parameters': ..., 'info': ...} if `path` is a file of this type, else False (the default: a type
+        that is not told from a path, as arrays, flat binary files and streams)"""
+        return False
+
     def get_diagnostics(self):
         """format-specific [{'name': ..., 'value': ...}, ...] (reference base/dataset.py:198-204)"""
         return []

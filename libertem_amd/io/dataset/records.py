@@ -1,6 +1,7 @@
 """
-RecordFileDataSet: what the formats share that are ONE file of fixed-size frame records (Norpix .seq, EMPAD .raw,
-NanoMegas .blo): a file header, then per frame `[frame header | pixels | frame footer]`.
+RecordFileDataSet: what the formats share that are files of fixed-size frame records (Norpix .seq, EMPAD .raw,
+NanoMegas .blo: one file; TVIPS: a series of files): a file header, then per frame
+`[frame header | pixels | frame footer]`.
 
 The reference strips headers and footers on the host, per tile and for every run, through numba read ranges
 (io/dataset/base/tiling.py, decode.py).  Here the file bytes go up once, whole records at a time, through the
@@ -8,10 +9,18 @@ pinned bounce buffers of `DecodedFileDataSet`, and `ltmi_records_gather` (csrc/l
 into one contiguous array behind each copy: a device-resident dataset of the file's own pixel type from then on,
 or one that is streamed per partition when it does not fit (decoded.py).
 
-A format hands `_record_layout()` what it read from its headers and gets the `FrameLayout` back, with
-`stride = frame_header + payload + frame_footer`; `_frame_source()` is implemented here, once.
+A format hands `_record_layout()` (one file) or `_segments_layout()` (a series) what it read from its headers and
+gets the `FrameLayout` back, with `stride = frame_header + payload + frame_footer`; `_frame_source()` is implemented
+here, once.
+
+The data of a set is an ordered list of `Segment`s `(path, file_header, first_frame, n_frames)`, one per file, that
+share the record geometry.  A chunk of the upload never spans two files -- `fill` hands back fewer frames than it
+was asked for at the end of a file (`locate`) --, so the bytes of a chunk are records one stride apart and the
+kernel's single stride holds.
 """
 import os
+from bisect import bisect_right
+from collections import namedtuple
 
 import numpy as np
 
@@ -37,6 +46,26 @@ def check_sig_shape(sig_shape, native):
     return tuple(sig_shape)
 
 
+#: one file of a set: its path, the bytes in front of its first record, the index of its first frame in the set and
+#: the records it holds
+Segment = namedtuple('Segment', 'path file_header first_frame n_frames')
+
+
+def locate(g, n_max, segments, stride):
+    """-> (segment index, byte offset, n): the file that holds frame `g` of the set, where its record starts in that
+    file, and how many of the `n_max` frames from `g` on that file holds.  `segments`: tuples
+    (path, file_header, first_frame, n_frames) in the order of their frames; integers only"""
+    if n_max < 1:
+        raise ValueError("n_max is %d" % n_max)
+    # (of files with the same first frame all but the last are empty: the rightmost is the one to take)
+    i = bisect_right([seg[2] for seg in segments], g) - 1
+    if i < 0 or not (segments[i][2] <= g < segments[i][2] + segments[i][3]):
+        raise IndexError("frame %d is in none of the %d files" % (g, len(segments)))
+    _, file_header, first_frame, n_frames = segments[i]
+    local = g - first_frame
+    return i, file_header + local * stride, min(n_max, n_frames - local)
+
+
 class RecordFileDataSet(DecodedFileDataSet):
     KIND = "record file"
     DECODE_KERNEL = "ltmi_records_gather"
@@ -54,6 +83,24 @@ class RecordFileDataSet(DecodedFileDataSet):
         """the geometry of the file `data_path` -> FrameLayout.  `n_frames`: records the file holds (the last one
         may lack its footer); `image_count`: what the dataset reports (default: `n_frames`), also the bound of
         `sync_offset`"""
+        return self._segments_layout(
+            [Segment(str(data_path), int(file_header), 0, int(n_frames))], frame_header, payload_bytes, frame_footer,
+            storage, native_shape, nav_shape, image_count)
+
+    def _segments_layout(self, segments, frame_header, payload_bytes, frame_footer, storage, native_shape,
+                         nav_shape, image_count=None):
+        """the geometry of a series of files -> FrameLayout.  `segments`: (path, file_header, first_frame,
+        n_frames) per file, in the order of their frames and without gaps; the record geometry is that of all of
+        them (the last record of the last file may lack its footer)"""
+        segments = [Segment(str(p), int(h), int(f), int(n)) for p, h, f, n in segments]
+        n_frames = 0
+        for seg in segments:
+            if seg.first_frame != n_frames or seg.n_frames < 0:
+                raise DataSetException("%s: frames %d to %d do not continue the %d frames before" % (
+                    seg.path, seg.first_frame, seg.first_frame + seg.n_frames, n_frames))
+            n_frames += seg.n_frames
+        if not segments:
+            raise DataSetException("a record dataset of no files")
         storage = np.dtype(storage)
         native = tuple(int(s) for s in native_shape)
         if int(prod(native)) * storage.itemsize != payload_bytes:
@@ -62,8 +109,10 @@ class RecordFileDataSet(DecodedFileDataSet):
         sig_shape = check_sig_shape(self._sig_arg, native)
         check_sync_offset(self._sync_offset_arg, image_count)
         self._image_count = image_count
-        self._records = dict(path=str(data_path), file_header=int(file_header), frame_header=int(frame_header),
-                             payload_bytes=int(payload_bytes), frame_footer=int(frame_footer))
+        # (`path` and `file_header`: of the first file -- the whole set for the one-file formats)
+        self._records = dict(path=segments[0].path, file_header=segments[0].file_header,
+                             frame_header=int(frame_header), payload_bytes=int(payload_bytes),
+                             frame_footer=int(frame_footer), segments=tuple(segments))
         return FrameLayout(
             nav_shape=tuple(int(n) for n in nav_shape), sig_shape=sig_shape, native_shape=native, storage=storage,
             stride=int(frame_header) + int(payload_bytes) + int(frame_footer), n_frames=int(n_frames),
@@ -82,15 +131,21 @@ class RecordFileDataSet(DecodedFileDataSet):
         from libertem_amd import hip
         rec = self._records
         stride = self._layout.stride
-        first, frame_header, payload = rec['file_header'], rec['frame_header'], rec['payload_bytes']
-        mapped = np.memmap(rec['path'], dtype=np.uint8, mode='r')
-        size = len(mapped)
+        segments, frame_header, payload = rec['segments'], rec['frame_header'], rec['payload_bytes']
+        # the frames of the layout that follow the last file's first one are that file's, as they always were (a
+        # layout may count a last record without its footer, which the whole records of a file size leave out)
+        last = segments[-1]
+        segments = segments[:-1] + (last._replace(n_frames=self._layout.n_frames - last.first_frame),)
+        mappings = {}                                 # one per file, opened when a chunk first needs it
 
-        def fill(pool, host, g, n):
-            # whole records; of the last one of the file, which may lack its footer, what the file holds (the
-            # kernel reads payloads only)
-            start = first + g * stride
-            _host_copy(pool, host, 0, mapped, start, min(n * stride, size - start))
+        def fill(pool, host, g, n_max):
+            # whole records of ONE file: a chunk ends where its file does.  Of the last record, which may lack
+            # its footer, what the file holds (the kernel reads payloads only)
+            i, start, n = locate(g, n_max, segments, stride)
+            mapped = mappings.get(i)
+            if mapped is None:
+                mapped = mappings[i] = np.memmap(segments[i].path, dtype=np.uint8, mode='r')
+            _host_copy(pool, host, 0, mapped, start, min(n * stride, len(mapped) - start))
             return n
 
         def decode(src_ptr, n, dst_ptr, stream):
