@@ -89,6 +89,13 @@ int ltmi_masks_create_dense(int device, const void *masks_host, int result_dtype
  * complex64 stacks whose neighbouring masks share pixels (rings, radial bins), the blocked image that
  * runs on the matrix cores; ltmi_apply_masks picks the blocked one when it exists.  Environment (read here): LTMI_SPARSE_BELL=0 / 1 never / always builds the blocked image,
  * LTMI_BELL_MAX_RATIO moves the padding-factor threshold (default 8).
+ * With LTMI_SPARSE_LABELS=1 a float32 stack that is a PARTITION -- no pixel is stored by two masks: the box masks of a
+ * binned detector, a polar rebinning map, hard-edged rings -- and got neither the blocked nor the scatter image gets a
+ * label image as well: a label and a weight per pixel, one multiply-add per labelled pixel (k_labels: uint8 / int8 /
+ * uint16 / int16 / float32 tiles, row lists too); ltmi_masks_kind then reports 4.  Like the gather kernel it multiplies
+ * stored entries only: an unlabelled non-finite pixel reaches no result, a stored zero weight times NaN is NaN.  Unset
+ * or 0 the image is never built: the route is not the default because it is not yet faster than the gather kernel.
+ * Both settings give valid results.
  */
 int ltmi_masks_create_csr(int device, const int64_t *indptr, const int64_t *indices,
                           const void *data, int result_dtype, int64_t n_px, int64_t n_masks,
@@ -156,7 +163,9 @@ int ltmi_masks_destroy(ltmi_masks *m);
 /* 0 = dense with float32 / complex64 results (f32 matrix cores), 1 = dense with any other result
  * dtype (float64, complex128 on real tiles, exactly representable integer sums: f64 matrix cores;
  * complex tiles and wider integers: VALU kernel), 2 = csr, 3 = csr with a banded dense image (see
- * ltmi_masks_set_sig_shape) */
+ * ltmi_masks_set_sig_shape), 4 = csr with a label image (a partition stack, see ltmi_masks_create_csr).  3 and 4 say
+ * which image the handle HOLDS, not what every product runs on: with kind 4, bool / 32- / 64-bit tiles, set_tuning 41 /
+ * 42 and a handle with ltmi_masks_set_dense_origin stay on the gather kernel (ltmi_masks_last_kernel names the route) */
 int ltmi_masks_kind(const ltmi_masks *m, int *kind);
 
 /* ---- the hot call -----------------------------------------------------------------------

@@ -202,6 +202,14 @@ void *scat_build(const int64_t *indptr, const int64_t *indices, const float *val
                  int64_t n_masks, int *err);
 void scat_destroy(void *set);
 int scat_apply(ltmi_masks *m, void *set, int cplx, const MaskCall &call, bool *handled);
+// partition stacks (no pixel stored by two masks: binning, polar maps, hard rings) as a label and a weight per pixel
+// (ltmi_labels.hip): float32 results, 1- / 2-byte integer and float32 frames
+bool labels_qualifies(const int64_t *indptr, int64_t n_px, int64_t n_masks);
+void *labels_build(const int64_t *indptr, const int64_t *indices, const float *vals, int64_t n_px, int64_t n_masks,
+                   int *err);
+void labels_destroy(void *image);
+bool labels_takes(int tile_dtype);
+int labels_apply(ltmi_masks *m, void *image, const MaskCall &call);
 // float32 frames x multi-group float32 stacks on the bf16 matrix cores, float32-accurate (ltmi_split.hip)
 bool split_selected(bool tuned);
 bool split_wanted(int n_cols, int64_t n_px);
@@ -271,7 +279,7 @@ int bell_apply(ltmi_masks *m, void *image, int cplx, const MaskCall &call, bool 
 // The opaque handle behind `ltmi_masks*` (shared by ltmi_dense.hip and ltmi_sparse.hip).
 struct ltmi_masks {
     int device = 0;
-    int kind = 0;            // 0 dense/MFMA-f32, 1 dense/generic, 2 csr (SELL image)
+    int kind = 0;            // 0 dense/MFMA-f32, 1 dense/generic, 2 csr (SELL image; ltmi_masks_kind: 3 banded, 4 labels)
     int result_dtype = 0;
     int64_t n_masks = 0, n_px = 0;
     // kind 0

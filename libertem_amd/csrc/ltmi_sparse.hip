@@ -63,6 +63,7 @@ struct CsrImage {
     DevBuf<int> active;         // chunks with entries, concatenated per pass
     DevBuf<int> active_off;     // [n_pass + 1]
     void *bell = nullptr;       // blocked image for the matrix-core kernel (ltmi_bell.hip) or null
+    void *labels = nullptr;     // ltmi_labels.hip: label + weight per pixel of a partition stack that has no other image
     // integer result dtypes: the values are held as doubles (f64 = 1) and a product whose every
     // partial sum stays below 2^52 is exact in the float64 gather kernel (see csr_apply)
     int int_result = 0;
@@ -324,6 +325,7 @@ int csr_destroy(ltmi_masks *m) {
     bell_destroy(c->bell);
     scat_destroy(c->scat);
     band_destroy(c->band);
+    labels_destroy(c->labels);
     band_free_csr(c->kept);
     delete c;
     m->csr = nullptr;
@@ -518,6 +520,11 @@ bool csr_has_band(const ltmi_masks *m) {
     return c && c->band;
 }
 
+bool csr_has_labels(const ltmi_masks *m) {
+    const CsrImage *c = (const CsrImage *)m->csr;
+    return c && c->labels;
+}
+
 // float32 frames: k_scatter only where the blocked image pads at least this much (per stored entry)
 static constexpr double SCAT_MIN_BELL_RATIO = 3.0;
 
@@ -605,6 +612,11 @@ int csr_apply(ltmi_masks *m, const MaskCall &call) {
         const int rc = bell_apply(m, c->bell, c->cplx, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
+    // a partition stack (it has none of the images above): one multiply-add per labelled pixel, stored entries only
+    // like the gather kernel (set_tuning 41 / 42 and a stack that stands for a dense one keep the gather kernel)
+    if (c->labels && labels_takes(tile_dtype) && m->tune_ksplit_ring != 41 && m->tune_ksplit_ring != 42 &&
+        !m->dense_origin)
+        return labels_apply(m, c->labels, f32);
     switch (tile_dtype) {
         case LTMI_BOOL:
         case LTMI_U8: return launch_sell<uint8_t>(m, c, f32);
@@ -835,6 +847,23 @@ static int create_csr(int device, const int64_t *indptr, const int64_t *indices,
             c->scat = ltmi::scat_build(indptr, indices, vals, nc, n_px, n_masks, &err);
             // (a failed build = no scatter image, like a failed float16 blocked image: the other kernels serve)
             if (!c->scat) (void)hipGetLastError();
+        }
+    }
+    // A float32 stack that got neither of the two and stores no pixel twice (binning, polar maps, hard rings) runs on
+    // the gather kernel.  LTMI_SPARSE_LABELS=1 gives it the label image of ltmi_labels.hip instead; unset or 0: never
+    // (k_labels is not yet faster than the gather kernel).
+    {
+        const char *force = getenv("LTMI_SPARSE_LABELS");
+        bool build = result_dtype == LTMI_F32 && !gather_only && !c->bell && !c->scat && force && force[0] == '1';
+        if (build) build = ltmi::labels_qualifies(indptr, n_px, n_masks);
+        if (build) {
+            int err = LTMI_OK;
+            c->labels = ltmi::labels_build(indptr, indices, vals, n_px, n_masks, &err);
+            if (!c->labels) {
+                ltmi::csr_destroy(m);
+                delete m;
+                return err;
+            }
         }
     }
     c->nnz_real = (double)nnz * nc;

@@ -229,3 +229,37 @@ def sparse_circular_multi_stack(mask_index, centerX, centerY, imageSizeX, imageS
         mask_index=mask_index, offsetX=np.array(centerX, dtype=int) - c,
         offsetY=np.array(centerY, dtype=int) - c, template=template,
         imageSizeX=imageSizeX, imageSizeY=imageSizeY)
+
+
+def bin_masks(sig_shape, bin_factor, dtype=np.float32):
+    """The box masks that bin a detector of `sig_shape` = (h, w) by `bin_factor` in both directions, weights 1: a
+    scipy CSR matrix (ceil(h / b) * ceil(w / b), h * w), one row per bin over the flattened frame, so that
+    `bin_masks(...) @ frame.ravel()` is the binned frame.  Mask k is bin (k // nx, k % nx) with nx = ceil(w / b); the
+    bins at the lower and right edge are partial where b does not divide the shape.  (The stack the reference's
+    examples/binning.ipynb builds layer by layer.)  A bare 2-D scipy matrix is ONE mask for ApplyMasksUDF:
+    `mask_factories=bin_masks_factory(sig, b)` hands the stack over as a stack."""
+    import scipy.sparse as sp
+    h, w = (int(s) for s in sig_shape)
+    b = int(bin_factor)
+    if b < 1 or h < 1 or w < 1:
+        raise ValueError(f"bin_masks: sig_shape {sig_shape!r}, bin_factor {bin_factor!r}")
+    ny, nx = -(-h // b), -(-w // b)
+    yy, xx = np.mgrid[0:h, 0:w]
+    label = ((yy // b) * nx + xx // b).ravel()
+    px = np.arange(h * w, dtype=np.int64)
+    return sp.csr_matrix((np.ones(h * w, dtype=dtype), (label, px)), shape=(ny * nx, h * w))
+
+
+def bin_masks_factory(sig_shape, bin_factor, dtype=np.float32):
+    """`mask_factories` for ApplyMasksUDF(..., use_sparse=True): a callable that gives bin_masks(...) as a SparseStack"""
+    def factory():
+        return SparseStack.from_csr_masks_by_px(bin_masks(sig_shape, bin_factor, dtype), sig_shape)
+    return factory
+
+
+def is_label_stack(csr_px_by_masks):
+    """Is a (n_px, n_masks) scipy CSR stack a partition -- a stored entry, and no pixel stored by two masks?  The rule
+    of the library (csrc/ltmi_labels.hip labels_qualifies) by which, with LTMI_SPARSE_LABELS=1, a float32 stack that got
+    no blocked / scatter image gets its label image; tests/test_label_kernels_gpu.py holds the two together."""
+    counts = np.diff(np.asarray(csr_px_by_masks.indptr))
+    return int(counts.sum()) > 0 and int(counts.max(initial=0)) <= 1
