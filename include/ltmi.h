@@ -557,6 +557,41 @@ int ltmi_crystallinity_corrected(ltmi_fft_plan *p, const void *tile, int tile_dt
  * frame on hipFFT.  The string lives as long as the plan. */
 const char *ltmi_fft_plan_last_kernel(const ltmi_fft_plan *p);
 
+/* ---- template matching at given peaks (hipFFT) ---------------------------------------------------
+ * A correlation plan owns a batched 2D real-to-complex and a complex-to-real hipFFT (frames of
+ * sig_h x sig_w float32, `max_batch` per execution), their workspace (f32 frames + complex64 half
+ * spectra of one batch) and the spectrum of ONE template.
+ * template_host: HOST float32 (sig_h, sig_w), centred at (sig_h/2, sig_w/2); the plan stores
+ * conj(rfft2(ifftshift(t))) / (sig_h sig_w) on the device, computed once with its own forward plan. */
+typedef struct ltmi_corr_plan ltmi_corr_plan;   /* opaque */
+int ltmi_corr_plan_create(int device, int sig_h, int sig_w, int max_batch, const float *template_host,
+                          ltmi_corr_plan **out);
+int ltmi_corr_plan_destroy(ltmi_corr_plan *p);
+/* For every frame f of the tile and every peak k:
+ *   corr = irfft2(rfft2((float)tile[f]) * conj(rfft2(ifftshift(t))))        (circular cross-correlation)
+ *   W = corr[py-r .. py+r, px-r .. px+r], clipped to the frame (no wrap-around), r = crop_radius
+ *   peak_values[f, k]     = max(W)
+ *   centers[f, k]         = (y, x) of the first maximum of W in row-major order, frame coordinates
+ *   refineds[f, k]        = centre of mass of N - min(N), N = the (2q+1)^2 neighbourhood of centers[f, k]
+ *                           clipped to the frame, q = refine_radius; centers[f, k] if the weights sum to 0
+ *   peak_elevations[f, k] = (max(W) - mean(W)) / std(W), ddof 0; 0 if std(W) is 0
+ * A frame with a non-finite pixel gets peak_values = NaN for every peak (its other results are then the
+ * window's first position and NaN); other frames are unaffected.
+ * tile: device (n_frames, sig_h*sig_w) of tile_dtype (the dtypes ltmi_crystallinity takes), ld_tile
+ * elements apart; peaks: device int32 (n_peaks, 2) of (py, px) inside the frame -- read back and checked
+ * by every call, which therefore waits for the work already on `stream`; centers: device int32
+ * (n_frames, n_peaks, 2); refineds: device float32 (n_frames, n_peaks, 2); peak_values, peak_elevations:
+ * device float32 (n_frames, n_peaks).  No atomics: the results of a call repeat bit for bit.
+ * A peak outside the frame, crop_radius < 1 or refine_radius < 1: LTMI_E_SHAPE. */
+int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t n_frames,
+                         int64_t ld_tile, const int32_t *peaks, int n_peaks, int crop_radius,
+                         int refine_radius, int32_t *centers, float *refineds, float *peak_values,
+                         float *peak_elevations, void *stream);
+/* The kernels of the last ltmi_correlate_peaks call of this plan:
+ * "k_corr_load<dtype> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=N" (csrc/ltmi_corr.hip).
+ * The string lives as long as the plan. */
+const char *ltmi_corr_plan_last_kernel(const ltmi_corr_plan *p);
+
 /* ---- multi-GPU: RCCL (over xGMI) behind the C ABI ---------------------------------------------
  * One process per GPU; the path shards over scan positions, the ranks exchange per-partition nav-grid
  * results only.  Replaces, for a reference-side binding, the transport of partition results through

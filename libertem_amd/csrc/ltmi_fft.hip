@@ -30,7 +30,7 @@ struct ltmi_fft_plan {
 
 namespace ltmi {
 
-static const char *fft_err(hipfftResult r) {
+const char *fft_err(hipfftResult r) {   // (shared with ltmi_corr.hip)
     switch (r) {
         case HIPFFT_SUCCESS: return "success";
         case HIPFFT_INVALID_PLAN: return "invalid plan";

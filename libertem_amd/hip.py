@@ -36,6 +36,7 @@ EXPORTS = (
     'ltmi_logsum_frames',
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_records_gather', 'ltmi_records_last_kernel', 'ltmi_transpose2d', 'ltmi_transpose_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
+    'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -312,6 +313,11 @@ def lib():
         L.ltmi_masks_last_kernel.restype = c.c_char_p
         L.ltmi_fft_plan_last_kernel.argtypes = [vp]
         L.ltmi_fft_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_corr_plan_create.argtypes = [i32, i32, i32, i32, vp, c.POINTER(vp)]
+        L.ltmi_corr_plan_destroy.argtypes = [vp]
+        L.ltmi_correlate_peaks.argtypes = [vp, vp, i32, i64, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.ltmi_corr_plan_last_kernel.argtypes = [vp]
+        L.ltmi_corr_plan_last_kernel.restype = c.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -937,6 +943,48 @@ class FFTPlan:
     def close(self):
         if self._ptr is not None and self._ptr.value:
             lib().ltmi_fft_plan_destroy(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CorrPlan:
+    """Owns one `ltmi_corr_plan*`: batched 2D R2C and C2R hipFFTs + workspace for frames of (sig_h, sig_w), and the
+    device spectrum of one template (host float32 (sig_h, sig_w), centred at (sig_h // 2, sig_w // 2))."""
+
+    def __init__(self, device, sig_h, sig_w, max_batch, template):
+        t = np.ascontiguousarray(template, dtype=np.float32)
+        if t.shape != (int(sig_h), int(sig_w)):
+            raise ValueError(f"template of shape {t.shape} for frames of {(int(sig_h), int(sig_w))}")
+        out = ctypes.c_void_p()
+        check(lib().ltmi_corr_plan_create(int(device), int(sig_h), int(sig_w), int(max_batch),
+                                          t.ctypes.data_as(ctypes.c_void_p), ctypes.byref(out)),
+              'ltmi_corr_plan_create')
+        self._ptr = out
+        self.device, self.sig, self.max_batch = int(device), (int(sig_h), int(sig_w)), int(max_batch)
+
+    def correlate_peaks(self, tile_ptr, tile_dtype, n_frames, ld_tile, peaks_ptr, n_peaks, crop_radius,
+                        refine_radius, centers_ptr, refineds_ptr, peak_values_ptr, peak_elevations_ptr,
+                        stream=None):
+        """peaks: device int32 (n_peaks, 2) of (py, px); centers int32 / refineds float32 (n_frames, n_peaks, 2),
+        peak_values / peak_elevations float32 (n_frames, n_peaks): device pointers (include/ltmi.h)."""
+        check(lib().ltmi_correlate_peaks(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), peaks_ptr, int(n_peaks),
+            int(crop_radius), int(refine_radius), centers_ptr, refineds_ptr, peak_values_ptr,
+            peak_elevations_ptr, stream if isinstance(stream, int) else _stream_ptr(stream)),
+            'ltmi_correlate_peaks')
+
+    def last_kernel(self):
+        """'k_corr_load<...> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=N'"""
+        return lib().ltmi_corr_plan_last_kernel(self._ptr).decode()
+
+    def close(self):
+        if self._ptr is not None and self._ptr.value:
+            lib().ltmi_corr_plan_destroy(self._ptr)
             self._ptr = None
 
     def __del__(self):

@@ -6,8 +6,9 @@ from libertem_amd.common.udf import UDFMethod
 from libertem_amd.common.exceptions import UDFRunCancelled, UDFException
 from .auto import AutoUDF
 from .record import RecordUDF
+from .correlation import CorrelationUDF, run_correlation
 
 __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPostprocessMixin', 'UDFPreprocessMixin',
            'UDFMergeAllMixin', 'UDFMeta', 'UDFRunner', 'UDFData', 'NoOpUDF', 'UDFMethod', 'check_cast', 'AutoUDF',
-           'RecordUDF',
+           'RecordUDF', 'CorrelationUDF', 'run_correlation',
            'UDFRunCancelled', 'UDFException']
