@@ -592,6 +592,38 @@ int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int tile_dtype, in
  * The string lives as long as the plan. */
 const char *ltmi_corr_plan_last_kernel(const ltmi_corr_plan *p);
 
+/* ---- lattice fit to the matched peaks -------------------------------------------------------------
+ * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]
+ * (1 where `weights` is NULL), integer lattice indices (i_k, j_k) = indices[k] (precondition |i|, |j| <= 2^20),
+ * a start lattice zero0, a0, b0 = start[0..1], start[2..3], start[4..5] as (y, x) and tolerance tau >= 0 in
+ * pixels; all arithmetic is float64, the results are cast once at the end:
+ *   1. p_k = zero0 + i_k a0 + j_k b0
+ *   2. selector[f, k] = 1 where r_k is finite in both components, w_k is finite, w_k > 0 and
+ *      |r_k - p_k|_2 <= tau -- and, where `peak_values` is not NULL, peak_values[f, k] is finite --, else 0
+ *   3. a fit EXISTS iff the index pairs of the selected peaks are not collinear, decided on the integers:
+ *      k0 = the first selected k, k1 = the first selected k with another index pair; some selected k has
+ *      (i_k - i_k0)(j_k1 - j_k0) - (j_k - j_k0)(i_k1 - i_k0) != 0 in int64.  (At least 3 peaks are then
+ *      selected, and the weighted normal matrix is positive definite: no floating-point threshold.)
+ *   4. if it exists: (zero, a, b)[f] minimises sum_sel w_k |zero + i_k a + j_k b - r_k|^2 -- the weight
+ *      multiplies the SQUARED residual -- and error[f] = sqrt(sum_sel w_k |res_k|^2 / sum_sel w_k)
+ *   5. otherwise zero, a, b and error of the frame are NaN; selector is as in step 2.
+ * refineds: device float32 (n_frames, n_peaks, 2); weights, peak_values: device float32 (n_frames, n_peaks) or
+ * NULL; indices: DEVICE int32 (n_peaks, 2); start: HOST, 6 doubles; zero, a, b: device float32 (n_frames, 2);
+ * selector: device bytes (n_frames, n_peaks), each 0 or 1; error: device float32 (n_frames).
+ * One launch of k_lattice_fit on `stream` (csrc/ltmi_lattice.hip: one wave per frame, float64 sums combined by a
+ * fixed-order shuffle tree, no atomics: the results of a call repeat bit for bit).  The indices never address
+ * memory, so nothing is read back and the stream is not drained.  n_frames == 0 or n_peaks == 0 launches nothing
+ * (with n_peaks == 0 the outputs are left as they are: LatticeRefineUDF refuses an empty index list).
+ * A null pointer other than weights / peak_values: LTMI_E_INVALID; n_frames < 0, n_peaks < 0, tolerance negative
+ * or NaN, a non-finite start value: LTMI_E_SHAPE. */
+int ltmi_lattice_fit(int device, const float *refineds, const float *weights, const float *peak_values,
+                     int64_t n_frames, int n_peaks, const int32_t *indices, const double *start,
+                     double tolerance, float *zero, float *a, float *b, uint8_t *selector, float *error,
+                     void *stream);
+/* "k_lattice_fit" after the first launch issued by the calling thread, "" before; unchanged by a call that
+ * launches nothing. */
+const char *ltmi_lattice_last_kernel(void);
+
 /* ---- multi-GPU: RCCL (over xGMI) behind the C ABI ---------------------------------------------
  * One process per GPU; the path shards over scan positions, the ranks exchange per-partition nav-grid
  * results only.  Replaces, for a reference-side binding, the transport of partition results through

@@ -37,6 +37,7 @@ EXPORTS = (
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_records_gather', 'ltmi_records_last_kernel', 'ltmi_transpose2d', 'ltmi_transpose_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
+    'ltmi_lattice_fit', 'ltmi_lattice_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -318,6 +319,9 @@ def lib():
         L.ltmi_correlate_peaks.argtypes = [vp, vp, i32, i64, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp]
         L.ltmi_corr_plan_last_kernel.argtypes = [vp]
         L.ltmi_corr_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_lattice_fit.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp, c.c_double, vp, vp, vp, vp, vp, vp]
+        L.ltmi_lattice_last_kernel.argtypes = []
+        L.ltmi_lattice_last_kernel.restype = c.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -992,6 +996,30 @@ class CorrPlan:
             self.close()
         except Exception:
             pass
+
+
+def lattice_fit(device, refineds_ptr, weights_ptr, peak_values_ptr, n_frames, n_peaks, indices_ptr, start, tolerance,
+                zero_ptr, a_ptr, b_ptr, selector_ptr, error_ptr, stream=None):
+    """The lattice zero + i a + j b that fits the peaks of every frame (include/ltmi.h).  refineds float32
+    (n_frames, n_peaks, 2), weights / peak_values float32 (n_frames, n_peaks) or None, indices int32 (n_peaks, 2),
+    zero / a / b float32 (n_frames, 2), selector bytes (n_frames, n_peaks), error float32 (n_frames): device
+    pointers; start: the six host values zero0, a0, b0 as (y, x) or None."""
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.float64).reshape(-1)
+        if start.size != 6:
+            raise ValueError(f"start holds zero0, a0, b0 as (y, x): 6 values, not {start.size}")
+        start_ptr = start.ctypes.data_as(ctypes.c_void_p)
+    else:
+        start_ptr = None
+    check(lib().ltmi_lattice_fit(
+        int(device), refineds_ptr, weights_ptr, peak_values_ptr, int(n_frames), int(n_peaks), indices_ptr,
+        start_ptr, float(tolerance), zero_ptr, a_ptr, b_ptr, selector_ptr, error_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_lattice_fit')
+
+
+def lattice_last_kernel():
+    """'k_lattice_fit' after the first launch of `lattice_fit` on this thread, '' before"""
+    return lib().ltmi_lattice_last_kernel().decode()
 
 
 def clear_last_runtime_error():
