@@ -592,6 +592,42 @@ int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int tile_dtype, in
  * The string lives as long as the plan. */
 const char *ltmi_corr_plan_last_kernel(const ltmi_corr_plan *p);
 
+/* ---- the strongest correlation maxima of every frame ---------------------
+ * For every map c of (h, w) float32, with N = num_peaks, d = min_distance, b = border, q = refine_radius:
+ *   1. p = (y, x) is a candidate iff, over every other p' with |y'-y| <= d and |x'-x| <= d inside the frame,
+ *      c[p] > c[p'] where p' precedes p in row-major order and c[p] >= c[p'] where it follows;
+ *   2. a candidate is eligible iff b <= y < h-b, b <= x < w-b and c[p] > threshold_abs;
+ *   3. the eligible candidates by value descending, then index ascending; v0 the first value; if v0 > 0 those with
+ *      c[p] < threshold_rel * v0 (one float32 multiply) go; the first N of the rest are kept: n_found[f];
+ *   4. for k < n_found[f]: centers[f, k] = (y, x), and peak_values, refineds, peak_elevations as ltmi_correlate_peaks
+ *      gives them for the peak centers[f, k] with crop_radius = d and refine_radius = q;
+ *   5. for k >= n_found[f]: centers (-1, -1), the rest NaN;
+ *   6. a map with a non-finite value has n_found = 0.
+ * maps: DEVICE float32, map f at maps + f * ld_map (rows contiguous).  n_found: device int32 (n_frames); centers:
+ * device int32 (n_frames, N, 2); refineds: device float32 (n_frames, N, 2); peak_values, peak_elevations: device
+ * float32 (n_frames, N).  Limits: N <= 1024, w <= 8192, h w <= 2^31 - 1; any d (any number of cells per frame).
+ * No atomics: the results of a call repeat bit for bit.  Nothing is read back and the stream is not drained; the
+ * candidate scratch (16 bytes per (d+1)^2 cell and frame, at most 256 MiB at a time) belongs to the calling thread.
+ * num_peaks outside [1, 1024], min_distance < 1, refine_radius < 1, border < 0 or 2 border >= min(h, w),
+ * threshold_rel outside [0, 1], a NaN threshold, ld_map < h w, n_frames < 0: LTMI_E_SHAPE; a null pointer:
+ * LTMI_E_INVALID.  n_frames == 0 launches nothing. */
+int ltmi_find_peaks_maps(int device, const float *maps, int64_t n_frames, int h, int w, int64_t ld_map,
+                         int num_peaks, int min_distance, int border, float threshold_abs, float threshold_rel,
+                         int refine_radius, int32_t *n_found, int32_t *centers, float *refineds,
+                         float *peak_values, float *peak_elevations, void *stream);
+/* "k_pf_cells + k_pf_verify + k_pf_select + k_corr_found" after the first launching ltmi_find_peaks_maps call of
+ * the calling thread, "" before. */
+const char *ltmi_find_peaks_last_kernel(void);
+/* The same search on the correlation maps of a tile: per batch the transforms of ltmi_correlate_peaks
+ * (k_corr_load, R2C, k_corr_mul, C2R), then the search on the plan's workspace.  There is no peak list to check, so
+ * nothing is read back and the stream is not drained.  ltmi_corr_plan_last_kernel then names
+ * "k_corr_load<dtype> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_pf_cells + k_pf_verify + k_pf_select +
+ * k_corr_found batch=N".  Errors as above; an unsupported tile dtype: LTMI_E_DTYPE; ld_tile < h w: LTMI_E_SHAPE. */
+int ltmi_correlate_find(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
+                        int num_peaks, int min_distance, int border, float threshold_abs, float threshold_rel,
+                        int refine_radius, int32_t *n_found, int32_t *centers, float *refineds, float *peak_values,
+                        float *peak_elevations, void *stream);
+
 /* ---- lattice fit to the matched peaks -------------------------------------------------------------
  * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]
  * (1 where `weights` is NULL), integer lattice indices (i_k, j_k) = indices[k] (precondition |i|, |j| <= 2^20),

@@ -272,6 +272,22 @@ int guard_list_rows(ltmi_masks *m, const void *target, int64_t ld_target, int64_
 int guard_deliver(ltmi_masks *m, void *out, int64_t ld_out, int64_t n_frames, int accumulate, hipStream_t stream);
 // ltmi_apply_masks without the guard (ltmi_dense.hip)
 int apply_masks_unguarded(ltmi_masks *m, const MaskCall &call);
+// the strongest local maxima of correlation maps (ltmi_peakfind.hip)
+struct PeakFind {
+    int n_peaks, d, border, q;             // d and q clamped to the frame's longer edge: the windows are clipped anyway
+    float threshold_abs, threshold_rel;
+};
+int peakfind_params(const char *who, int h, int w, int num_peaks, int min_distance, int border, float threshold_abs,
+                    float threshold_rel, int refine_radius, PeakFind *out);
+const char *peakfind_kernels();            // "k_pf_cells + k_pf_verify + k_pf_select + k_corr_found"
+// n_frames maps of (h, w) float32, ld_map elements apart -> the five results; `scratch` grows to two keys per cell
+int peakfind_search(const float *maps, int64_t n_frames, int h, int w, int64_t ld_map, const PeakFind &pf,
+                    DevBuf<uint64_t> &scratch, int32_t *n_found, int32_t *centers, float *refineds,
+                    float *peak_values, float *peak_elevations, hipStream_t stream);
+// ... its last step: the window statistics of the found peaks, on the code of k_corr_peaks (ltmi_corr.hip)
+int corr_found_stats(const float *maps, int64_t n_frames, int h, int w, int64_t ld_map, const PeakFind &pf,
+                     const int32_t *n_found, int32_t *centers, float *refineds, float *peak_values,
+                     float *peak_elevations, hipStream_t stream);
 // sparse frames against a dense stack (ltmi_csrframes.hip): the pixel-major image of the handle
 int bell_apply(ltmi_masks *m, void *image, int cplx, const MaskCall &call, bool *handled);
 }  // namespace ltmi

@@ -5,6 +5,8 @@
 // every expected peak, the maximum, its position, a centre-of-mass refinement and the elevation of the maximum over
 // the window.  Per batch of frames: k_corr_load (native pixels -> f32), hipFFT R2C, k_corr_mul, hipFFT C2R back into
 // the frame workspace, k_corr_peaks (one wave per (frame, peak)).  The correlation never leaves the plan's workspace.
+// ltmi_correlate_find (section 4.6d) runs the same transforms and then, in place of k_corr_peaks, the search of
+// ltmi_peakfind.hip for the strongest local maxima of every map, rated by k_corr_found on the window code of k_corr_peaks.
 #include "ltmi_common.h"
 #include <hipfft/hipfft.h>
 #include <algorithm>
@@ -19,6 +21,7 @@ struct ltmi_corr_plan {
     ltmi::DevBuf<float> real_buf;      // (batch, h, w) f32: the frames, then their correlations
     ltmi::DevBuf<hipfftComplex> spec;  // (batch, h, wc) c64
     ltmi::DevBuf<hipfftComplex> tspec; // (h, wc): conj(rfft2(ifftshift(t))) / (h w)
+    ltmi::DevBuf<uint64_t> cand;       // candidate keys of ltmi_correlate_find (ltmi_peakfind.hip), grown on demand
     hipStream_t bound_stream = nullptr;
     bool stream_bound = false;
     char last_kernel[128] = {0};
@@ -81,22 +84,15 @@ k_corr_mul(hipfftComplex *__restrict__ spec, const hipfftComplex *__restrict__ t
     }
 }
 
-// One wave per (frame, peak).  The lanes stride the window (row-major, clipped to the frame) and keep the maximum, the
-// first index that holds it, and the float64 sums of (v - v0) and (v - v0)^2 about the window's first value v0; a
-// fixed-order shuffle tree combines the lanes.  Lane 0 then takes the centre of mass of the (2q+1)^2 neighbourhood of
-// the maximum and stores the four results.  A non-finite value in the window (a frame with a non-finite pixel: the
-// transforms carry it to every value of its correlation) gives peak_value = NaN.
-__global__ void __launch_bounds__(256)
-k_corr_peaks(const float *__restrict__ corr, int h, int w, int64_t n_frames, const int32_t *__restrict__ peaks,
-             int n_peaks, int r, int q, int32_t *__restrict__ centers, float *__restrict__ refineds,
-             float *__restrict__ peak_values, float *__restrict__ peak_elevations) {
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= n_frames * n_peaks) return;                    // (the whole wave)
-    const int64_t f = g / n_peaks;
-    const int k = (int)(g - f * n_peaks);
-    const float *c = corr + f * (int64_t)h * w;
-    const int py = peaks[2 * k], px = peaks[2 * k + 1];
+// The statistics of one window, by one wave: the lanes stride the window of radius r around (py, px) (row-major, clipped
+// to the frame) and keep the maximum, the first index that holds it, and the float64 sums of (v - v0) and (v - v0)^2
+// about the window's first value v0; a fixed-order shuffle tree combines the lanes.  Lane 0 then takes the centre of
+// mass of the (2q+1)^2 neighbourhood of the maximum and stores the four results at slot `o`.  A non-finite value in the
+// window (a frame with a non-finite pixel: the transforms carry it to every value of its correlation) gives
+// peak_value = NaN.  Shared by k_corr_peaks and k_corr_found: the same instructions, so the same bits.
+__device__ __forceinline__ void corr_window(const float *c, int h, int w, int py, int px, int r, int q, int lane,
+                                            int64_t o, int32_t *centers, float *refineds, float *peak_values,
+                                            float *peak_elevations) {
     // (the host has checked the peak; the clamps keep a bad one inside the frame all the same)
     const int y0 = min(max(py - r, 0), h - 1), y1 = max(min(py + r, h - 1), y0);
     const int x0 = min(max(px - r, 0), w - 1), x1 = max(min(px + r, w - 1), x0);
@@ -132,7 +128,6 @@ k_corr_peaks(const float *__restrict__ corr, int h, int w, int64_t n_frames, con
     }
     bad = __any(bad);
     if (lane != 0) return;
-    const int64_t o = f * n_peaks + k;
     if (bad || best_i >= cnt) {
         const float nan = __builtin_nanf("");
         centers[2 * o] = y0;
@@ -168,6 +163,50 @@ k_corr_peaks(const float *__restrict__ corr, int h, int w, int64_t n_frames, con
     refineds[2 * o + 1] = flat ? (float)cx : (float)(sx / sw);
     peak_values[o] = best;
     peak_elevations[o] = sd > 0.0 ? (float)((((double)best - (double)v0) - mean_d) / sd) : 0.f;
+}
+
+// One wave per (frame, peak); peak k of frame f is peaks[f * peaks_stride + 2 k ..] (stride 0: one list for all frames).
+__global__ void __launch_bounds__(256)
+k_corr_peaks(const float *__restrict__ corr, int h, int w, int64_t n_frames, const int32_t *__restrict__ peaks,
+             int64_t peaks_stride, int n_peaks, int r, int q, int32_t *__restrict__ centers,
+             float *__restrict__ refineds, float *__restrict__ peak_values, float *__restrict__ peak_elevations) {
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= n_frames * n_peaks) return;                    // (the whole wave)
+    const int64_t f = g / n_peaks;
+    const int k = (int)(g - f * n_peaks);
+    const int32_t *pk = peaks + f * peaks_stride + 2 * k;
+    corr_window(corr + f * (int64_t)h * w, h, w, pk[0], pk[1], r, q, lane, f * n_peaks + k, centers, refineds,
+                peak_values, peak_elevations);
+}
+
+// The same for the peaks a search found (section 4.6d): slot k < n_found[f] of frame f holds its centre in `centers`
+// and gets the statistics of the window of radius r around it -- by step 1 of the search its first maximum is the
+// centre itself, so the slot's centre is rewritten with the same value --; the other slots become (-1, -1) and NaN.
+__global__ void __launch_bounds__(256)
+k_corr_found(const float *__restrict__ maps, int64_t ld_map, int h, int w, int64_t n_frames,
+             const int32_t *__restrict__ n_found, int n_peaks, int r, int q, int32_t *centers, float *refineds,
+             float *peak_values, float *peak_elevations) {
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= n_frames * n_peaks) return;                    // (the whole wave)
+    const int64_t f = g / n_peaks;
+    const int k = (int)(g - f * n_peaks);
+    const int64_t o = f * n_peaks + k;
+    if (k >= n_found[f]) {
+        if (lane == 0) {
+            const float nan = __builtin_nanf("");
+            centers[2 * o] = -1;
+            centers[2 * o + 1] = -1;
+            refineds[2 * o] = nan;
+            refineds[2 * o + 1] = nan;
+            peak_values[o] = nan;
+            peak_elevations[o] = nan;
+        }
+        return;
+    }
+    const int py = centers[2 * o], px = centers[2 * o + 1];
+    corr_window(maps + f * ld_map, h, w, py, px, r, q, lane, o, centers, refineds, peak_values, peak_elevations);
 }
 
 template <typename T>
@@ -296,6 +335,38 @@ extern "C" const char *ltmi_corr_plan_last_kernel(const ltmi_corr_plan *p) {
     return p ? p->last_kernel : "";
 }
 
+// the plan's two transforms run on `stream` from here on
+static int corr_bind_stream(ltmi_corr_plan *p, hipStream_t stream) {
+    if (!p->stream_bound || p->bound_stream != stream) {
+        hipfftResult s = hipfftSetStream(p->fwd, stream);
+        if (s == HIPFFT_SUCCESS) s = hipfftSetStream(p->inv, stream);
+        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(s));
+        p->bound_stream = stream;
+        p->stream_bound = true;
+    }
+    return LTMI_OK;
+}
+
+// n <= batch frames at `src` -> their correlation maps in real_buf: k_corr_load, R2C, k_corr_mul, C2R
+static int corr_transform(ltmi_corr_plan *p, const void *src, int tile_dtype, int64_t ld_tile, int64_t n,
+                          hipStream_t stream) {
+    const int64_t n_px = (int64_t)p->h * p->w;
+    const int rc = corr_load(src, tile_dtype, ld_tile, n, n_px, p->real_buf, stream);
+    if (rc != LTMI_OK) return rc;
+    if (n < p->batch) {
+        // the plans always transform `batch` frames: the unused tail holds zeros, not what an earlier batch
+        // left there (its transforms are never read)
+        LTMI_HIP(hipMemsetAsync(p->real_buf + n * n_px, 0, (size_t)(p->batch - n) * n_px * sizeof(float), stream));
+    }
+    hipfftResult s = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
+    if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(s));
+    corr_mul(p, n, stream);
+    LTMI_HIP(hipGetLastError());
+    s = hipfftExecC2R(p->inv, p->spec, p->real_buf);
+    if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecC2R failed: %s", fft_err(s));
+    return LTMI_OK;
+}
+
 extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t n_frames,
                                     int64_t ld_tile, const int32_t *peaks, int n_peaks, int crop_radius,
                                     int refine_radius, int32_t *centers, float *refineds, float *peak_values,
@@ -327,13 +398,8 @@ extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int til
     // (windows and neighbourhoods are clipped to the frame: a radius beyond its longer edge changes nothing)
     const int r = std::min(crop_radius, std::max(p->h, p->w));
     const int q = std::min(refine_radius, std::max(p->h, p->w));
-    if (!p->stream_bound || p->bound_stream != stream) {
-        hipfftResult s = hipfftSetStream(p->fwd, stream);
-        if (s == HIPFFT_SUCCESS) s = hipfftSetStream(p->inv, stream);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(s));
-        p->bound_stream = stream;
-        p->stream_bound = true;
-    }
+    const int rc_bind = corr_bind_stream(p, stream);
+    if (rc_bind != LTMI_OK) return rc_bind;
     snprintf(p->last_kernel, sizeof(p->last_kernel),
              "k_corr_load<%s> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=%d", dtype_name(tile_dtype),
              p->batch);
@@ -341,25 +407,62 @@ extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int til
     for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
         const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
         const void *src = (const char *)tile + (size_t)f0 * ld_tile * esz;
-        const int rc = corr_load(src, tile_dtype, ld_tile, n, n_px, p->real_buf, stream);
+        const int rc = corr_transform(p, src, tile_dtype, ld_tile, n, stream);
         if (rc != LTMI_OK) return rc;
-        if (n < p->batch) {
-            // the plans always transform `batch` frames: the unused tail holds zeros, not what an earlier batch
-            // left there (its transforms are never read)
-            LTMI_HIP(hipMemsetAsync(p->real_buf + n * n_px, 0, (size_t)(p->batch - n) * n_px * sizeof(float), stream));
-        }
-        hipfftResult s = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(s));
-        corr_mul(p, n, stream);
-        LTMI_HIP(hipGetLastError());
-        s = hipfftExecC2R(p->inv, p->spec, p->real_buf);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecC2R failed: %s", fft_err(s));
         const int64_t waves = n * n_peaks;
         hipLaunchKernelGGL(k_corr_peaks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream,
-                           (const float *)p->real_buf, p->h, p->w, n, peaks, n_peaks, r, q,
+                           (const float *)p->real_buf, p->h, p->w, n, peaks, (int64_t)0, n_peaks, r, q,
                            centers + 2 * f0 * n_peaks, refineds + 2 * f0 * n_peaks, peak_values + f0 * n_peaks,
                            peak_elevations + f0 * n_peaks);
         LTMI_HIP(hipGetLastError());
+    }
+    return LTMI_OK;
+}
+
+// the statistics of the peaks a search found, for ltmi_peakfind.hip
+int ltmi::corr_found_stats(const float *maps, int64_t n_frames, int h, int w, int64_t ld_map, const PeakFind &pf,
+                           const int32_t *n_found, int32_t *centers, float *refineds, float *peak_values,
+                           float *peak_elevations, hipStream_t stream) {
+    const int64_t waves = n_frames * pf.n_peaks;
+    hipLaunchKernelGGL(k_corr_found, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, maps, ld_map, h, w,
+                       n_frames, n_found, pf.n_peaks, pf.d, pf.q, centers, refineds, peak_values, peak_elevations);
+    LTMI_HIP(hipGetLastError());
+    return LTMI_OK;
+}
+
+extern "C" int ltmi_correlate_find(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t n_frames,
+                                   int64_t ld_tile, int num_peaks, int min_distance, int border, float threshold_abs,
+                                   float threshold_rel, int refine_radius, int32_t *n_found, int32_t *centers,
+                                   float *refineds, float *peak_values, float *peak_elevations, void *stream_) {
+    if (!p) LTMI_FAIL(LTMI_E_INVALID, "ltmi_correlate_find: null plan");
+    if (n_frames < 0) LTMI_FAIL(LTMI_E_SHAPE, "ltmi_correlate_find: negative frame count");
+    PeakFind pf;
+    int rc = peakfind_params("ltmi_correlate_find", p->h, p->w, num_peaks, min_distance, border, threshold_abs,
+                             threshold_rel, refine_radius, &pf);
+    if (rc != LTMI_OK) return rc;
+    if (!corr_takes(tile_dtype))
+        LTMI_FAIL(LTMI_E_DTYPE, "ltmi_correlate_find: unsupported tile dtype %s", dtype_name(tile_dtype));
+    const int64_t n_px = (int64_t)p->h * p->w;
+    if (ld_tile < n_px) LTMI_FAIL(LTMI_E_SHAPE, "ltmi_correlate_find: ld_tile < frame size");
+    if (n_frames == 0) return LTMI_OK;
+    if (!tile || !n_found || !centers || !refineds || !peak_values || !peak_elevations)
+        LTMI_FAIL(LTMI_E_INVALID, "ltmi_correlate_find: null pointer");
+    LTMI_HIP(hipSetDevice(p->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    rc = corr_bind_stream(p, stream);
+    if (rc != LTMI_OK) return rc;
+    snprintf(p->last_kernel, sizeof(p->last_kernel),
+             "k_corr_load<%s> + hipfft_r2c + k_corr_mul + hipfft_c2r + %s batch=%d", dtype_name(tile_dtype),
+             peakfind_kernels(), p->batch);
+    const size_t esz = (size_t)dtype_size(tile_dtype);
+    const int64_t N = pf.n_peaks;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
+        const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
+        rc = corr_transform(p, (const char *)tile + (size_t)f0 * ld_tile * esz, tile_dtype, ld_tile, n, stream);
+        if (rc != LTMI_OK) return rc;
+        rc = peakfind_search(p->real_buf, n, p->h, p->w, n_px, pf, p->cand, n_found + f0, centers + 2 * f0 * N,
+                             refineds + 2 * f0 * N, peak_values + f0 * N, peak_elevations + f0 * N, stream);
+        if (rc != LTMI_OK) return rc;
     }
     return LTMI_OK;
 }

@@ -38,6 +38,7 @@ EXPORTS = (
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
     'ltmi_lattice_fit', 'ltmi_lattice_last_kernel',
+    'ltmi_find_peaks_maps', 'ltmi_find_peaks_last_kernel', 'ltmi_correlate_find',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -322,6 +323,12 @@ def lib():
         L.ltmi_lattice_fit.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp, c.c_double, vp, vp, vp, vp, vp, vp]
         L.ltmi_lattice_last_kernel.argtypes = []
         L.ltmi_lattice_last_kernel.restype = c.c_char_p
+        L.ltmi_find_peaks_maps.argtypes = [i32, vp, i64, i32, i32, i64, i32, i32, i32, c.c_float, c.c_float, i32,
+                                           vp, vp, vp, vp, vp, vp]
+        L.ltmi_find_peaks_last_kernel.argtypes = []
+        L.ltmi_find_peaks_last_kernel.restype = c.c_char_p
+        L.ltmi_correlate_find.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, c.c_float, c.c_float, i32,
+                                          vp, vp, vp, vp, vp, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -982,8 +989,21 @@ class CorrPlan:
             peak_elevations_ptr, stream if isinstance(stream, int) else _stream_ptr(stream)),
             'ltmi_correlate_peaks')
 
+    def find_peaks(self, tile_ptr, tile_dtype, n_frames, ld_tile, num_peaks, min_distance, border, threshold_abs,
+                   threshold_rel, refine_radius, n_found_ptr, centers_ptr, refineds_ptr, peak_values_ptr,
+                   peak_elevations_ptr, stream=None):
+        """The num_peaks strongest local maxima of every frame's correlation map.  n_found
+        int32 (n_frames), centers int32 / refineds float32 (n_frames, num_peaks, 2), peak_values / peak_elevations
+        float32 (n_frames, num_peaks): device pointers (include/ltmi.h)."""
+        check(lib().ltmi_correlate_find(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), int(num_peaks),
+            int(min_distance), int(border), float(threshold_abs), float(threshold_rel), int(refine_radius),
+            n_found_ptr, centers_ptr, refineds_ptr, peak_values_ptr, peak_elevations_ptr,
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_correlate_find')
+
     def last_kernel(self):
-        """'k_corr_load<...> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=N'"""
+        """'k_corr_load<...> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=N'; after `find_peaks` the
+        search kernels 'k_pf_cells + k_pf_verify + k_pf_select + k_corr_found' stand in place of k_corr_peaks"""
         return lib().ltmi_corr_plan_last_kernel(self._ptr).decode()
 
     def close(self):
@@ -996,6 +1016,24 @@ class CorrPlan:
             self.close()
         except Exception:
             pass
+
+
+def find_peaks_maps(device, maps_ptr, n_frames, h, w, ld_map, num_peaks, min_distance, border, threshold_abs,
+                    threshold_rel, refine_radius, n_found_ptr, centers_ptr, refineds_ptr, peak_values_ptr,
+                    peak_elevations_ptr, stream=None):
+    """`CorrPlan.find_peaks` on float32 maps the caller supplies: map f of (h, w) at maps + f * ld_map elements
+    (include/ltmi.h)."""
+    check(lib().ltmi_find_peaks_maps(
+        int(device), maps_ptr, int(n_frames), int(h), int(w), int(ld_map), int(num_peaks), int(min_distance),
+        int(border), float(threshold_abs), float(threshold_rel), int(refine_radius), n_found_ptr, centers_ptr,
+        refineds_ptr, peak_values_ptr, peak_elevations_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_find_peaks_maps')
+
+
+def find_peaks_last_kernel():
+    """'k_pf_cells + k_pf_verify + k_pf_select + k_corr_found' after the first launching `find_peaks_maps` call
+    on this thread, '' before"""
+    return lib().ltmi_find_peaks_last_kernel().decode()
 
 
 def lattice_fit(device, refineds_ptr, weights_ptr, peak_values_ptr, n_frames, n_peaks, indices_ptr, start, tolerance,

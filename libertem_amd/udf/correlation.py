@@ -45,6 +45,16 @@ def _plan(device, sig, batch, template):
     return plan
 
 
+def plan_for(udf, sig, template):
+    """the cached plan of a UDF's device, frame shape, template and batch: as many frames as the workspace budget,
+    the tile depth and the partition allow"""
+    device = udf.meta.gpu_id if udf.meta.gpu_id is not None else 0
+    per_frame = sig[0] * sig[1] * 4 + sig[0] * (sig[1] // 2 + 1) * 8
+    depth = int(udf.meta.tiling_scheme.depth) if udf.meta.tiling_scheme is not None else 1
+    batch = max(1, min(CORR_WORKSPACE_BYTES // per_frame, depth, int(udf.meta.partition_shape[0])))
+    return _plan(device, sig, batch, template)
+
+
 def _window(p, radius, size):
     return max(p - radius, 0), min(p + radius, size - 1) + 1
 
@@ -158,11 +168,7 @@ class CorrelationUDF(UDF):
             raise ValueError(f"crop_radius {r} and refine_radius {q} must be at least 1")
         td = {'sig': sig, 'template': template, 'peaks': peaks, 'r': r, 'q': q}
         if runs_on_hip(self):
-            device = self.meta.gpu_id if self.meta.gpu_id is not None else 0
-            per_frame = sig[0] * sig[1] * 4 + sig[0] * (sig[1] // 2 + 1) * 8
-            depth = int(self.meta.tiling_scheme.depth) if self.meta.tiling_scheme is not None else 1
-            batch = max(1, min(CORR_WORKSPACE_BYTES // per_frame, depth, int(self.meta.partition_shape[0])))
-            td.update(plan=_plan(device, sig, batch, template), device_peaks={})
+            td.update(plan=plan_for(self, sig, template), device_peaks={})
         return td
 
     def process_tile(self, tile):
