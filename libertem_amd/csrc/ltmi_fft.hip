@@ -54,42 +54,44 @@ __global__ void __launch_bounds__(256)
 k_fft_prepare(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_px,
               const float *__restrict__ real_mask, float *__restrict__ out, int vec_ok,
               const double *__restrict__ dark, const double *__restrict__ gain) {
-    const int64_t f = blockIdx.y;
-    const T *src = tile + f * ld;
-    float *dst = out + f * n_px;
     const int64_t n8 = vec_ok ? n_px / 8 : 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-        T raw[8];
-        typedef T __attribute__((ext_vector_type(8))) vec_t;
-        *(vec_t *)raw = __builtin_nontemporal_load((const vec_t *)(src + i * 8));
-        float v[8];
-        if (dark || gain) {
+    // (the grid's y extent is capped at PREPARE_MAX_GRID_Y: a block walks every gridDim.y-th frame)
+    for (int64_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+        const T *src = tile + f * ld;
+        float *dst = out + f * n_px;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+            T raw[8];
+            typedef T __attribute__((ext_vector_type(8))) vec_t;
+            *(vec_t *)raw = __builtin_nontemporal_load((const vec_t *)(src + i * 8));
+            float v[8];
+            if (dark || gain) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const double d = dark ? dark[i * 8 + j] : 0.0;
-                const double g = gain ? gain[i * 8 + j] : 1.0;
-                v[j] = (float)(((double)raw[j] - d) * g);
+                for (int j = 0; j < 8; ++j) {
+                    const double d = dark ? dark[i * 8 + j] : 0.0;
+                    const double g = gain ? gain[i * 8 + j] : 1.0;
+                    v[j] = (float)(((double)raw[j] - d) * g);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (float)raw[j];
             }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (float)raw[j];
+            if (real_mask) {
+                const float4 m0 = *(const float4 *)(real_mask + i * 8);
+                const float4 m1 = *(const float4 *)(real_mask + i * 8 + 4);
+                v[0] *= m0.x; v[1] *= m0.y; v[2] *= m0.z; v[3] *= m0.w;
+                v[4] *= m1.x; v[5] *= m1.y; v[6] *= m1.z; v[7] *= m1.w;
+            }
+            *(float4 *)(dst + i * 8) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4 *)(dst + i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
-        if (real_mask) {
-            const float4 m0 = *(const float4 *)(real_mask + i * 8);
-            const float4 m1 = *(const float4 *)(real_mask + i * 8 + 4);
-            v[0] *= m0.x; v[1] *= m0.y; v[2] *= m0.z; v[3] *= m0.w;
-            v[4] *= m1.x; v[5] *= m1.y; v[6] *= m1.z; v[7] *= m1.w;
+        for (int64_t p = n8 * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px;
+             p += (int64_t)gridDim.x * 256) {
+            float v = (dark || gain)
+                          ? (float)(((double)src[p] - (dark ? dark[p] : 0.0)) * (gain ? gain[p] : 1.0))
+                          : (float)src[p];
+            if (real_mask) v *= real_mask[p];
+            dst[p] = v;
         }
-        *(float4 *)(dst + i * 8) = make_float4(v[0], v[1], v[2], v[3]);
-        *(float4 *)(dst + i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-    for (int64_t p = n8 * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px;
-         p += (int64_t)gridDim.x * 256) {
-        float v = (dark || gain)
-                      ? (float)(((double)src[p] - (dark ? dark[p] : 0.0)) * (gain ? gain[p] : 1.0))
-                      : (float)src[p];
-        if (real_mask) v *= real_mask[p];
-        dst[p] = v;
     }
 }
 
@@ -112,21 +114,24 @@ k_fft_prepare_corr(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int
         g[j] = gain ? gain[p0 + j] : 1.0;
         m[j] = real_mask ? real_mask[p0 + j] : 1.f;
     }
-    const int64_t f0 = (int64_t)blockIdx.y * frames_per_block;
-    const int64_t f1 = min<int64_t>(n_frames, f0 + frames_per_block);
     typedef T __attribute__((ext_vector_type(8))) vec_t;
+    // (the grid's y extent is capped at PREPARE_MAX_GRID_Y: a block walks every gridDim.y-th group of frames)
+    for (int64_t f0 = (int64_t)blockIdx.y * frames_per_block; f0 < n_frames;
+         f0 += (int64_t)gridDim.y * frames_per_block) {
+        const int64_t f1 = min<int64_t>(n_frames, f0 + frames_per_block);
 #pragma unroll 2
-    for (int64_t f = f0; f < f1; ++f) {
-        const vec_t x = __builtin_nontemporal_load((const vec_t *)(tile + f * ld + p0));
-        float v[8];
+        for (int64_t f = f0; f < f1; ++f) {
+            const vec_t x = __builtin_nontemporal_load((const vec_t *)(tile + f * ld + p0));
+            float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            v[j] = (float)(((double)x[j] - d[j]) * g[j]);
-            if (real_mask) v[j] *= m[j];
+            for (int j = 0; j < 8; ++j) {
+                v[j] = (float)(((double)x[j] - d[j]) * g[j]);
+                if (real_mask) v[j] *= m[j];
+            }
+            float *dst = out + f * n_px + p0;
+            *(float4 *)dst = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4 *)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
-        float *dst = out + f * n_px + p0;
-        *(float4 *)dst = make_float4(v[0], v[1], v[2], v[3]);
-        *(float4 *)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
     }
 }
 
@@ -195,6 +200,10 @@ struct FftCorr {                   // detector corrections fused into the prepar
     int n_excl = 0, max_env = 0;
 };
 
+// gridDim.y of the two prepare kernels: the frames of a batch (max_batch of the plan, which nothing bounds) beyond it
+// are walked by the kernels' frame loops
+constexpr int64_t PREPARE_MAX_GRID_Y = 65535;
+
 template <typename T>
 static int run_prepare(const void *tile, int64_t ld, int64_t n, int64_t n_px, const float *real_mask,
                        float *out, hipStream_t stream, const FftCorr &corr) {
@@ -204,11 +213,11 @@ static int run_prepare(const void *tile, int64_t ld, int64_t n, int64_t n_px, co
     if ((corr.dark || corr.gain) && vec_ok) {
         const int fpb = 16;
         const unsigned bx = (unsigned)((n_px / 8 + 255) / 256);
-        hipLaunchKernelGGL((k_fft_prepare_corr<T>), dim3(bx, (unsigned)((n + fpb - 1) / fpb)),
+        hipLaunchKernelGGL((k_fft_prepare_corr<T>), dim3(bx, (unsigned)std::min<int64_t>((n + fpb - 1) / fpb, PREPARE_MAX_GRID_Y)),
                            dim3(256), 0, stream, (const T *)tile, ld, n, n_px, real_mask, out,
                            corr.dark, corr.gain, fpb);
     } else {
-        hipLaunchKernelGGL((k_fft_prepare<T>), dim3(gx, (unsigned)n), dim3(256), 0, stream,
+        hipLaunchKernelGGL((k_fft_prepare<T>), dim3(gx, (unsigned)std::min<int64_t>(n, PREPARE_MAX_GRID_Y)), dim3(256), 0, stream,
                            (const T *)tile, ld, n, n_px, real_mask, out, vec_ok, corr.dark,
                            corr.gain);
     }

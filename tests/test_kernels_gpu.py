@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import recipes
+from cryst_ref import _cryst_reference, _cryst_run
 from oracle import path as opath
 
 torch = pytest.importorskip("torch")
@@ -1857,37 +1858,7 @@ def test_row_lists_for_the_blocked_sparse_kernel(hip, tile_dtype, n_frames):
 
 
 # --- CrystallinityUDF in one kernel (csrc/ltmi_cryst.hip) ----------------
-def _cryst_reference(frames, rad_in, rad_out, real):
-    """float64 restatement of udf/crystallinity.py:47-79 through the oracle's mask construction"""
-    from libertem_amd.udf.crystallinity import crystallinity_masks
-    sig = frames.shape[-2:]
-    real_mask, half = crystallinity_masks(sig, rad_in, rad_out, real[0] if real else None,
-                                          real[1] if real else None)
-    out = np.zeros(len(frames))
-    for i, fr in enumerate(frames.astype(np.float64)):
-        out[i] = np.sum(abs(np.fft.rfft2(fr * real_mask if real_mask is not None else fr)) * half)
-    return out, real_mask, half
-
-
-def _cryst_run(hip, frames, real_mask, half, accumulate_into=None, ld_pad=0, batch=64):
-    from libertem_amd.udf.crystallinity import mask_box
-    n, h, w = frames.shape
-    plan = hip.FFTPlan(0, h, w, batch)
-    ld = h * w + ld_pad
-    padded = np.zeros((n, ld), dtype=frames.dtype)
-    padded[:, :h * w] = frames.reshape(n, -1)
-    t = _dev(padded)
-    rm = None if real_mask is None else torch.from_numpy(
-        np.ascontiguousarray(real_mask.astype(np.float32))).cuda()
-    hm = torch.from_numpy(np.ascontiguousarray(half.astype(np.float32))).cuda()
-    out = torch.full((n,), 7.0, dtype=torch.float32, device='cuda') if accumulate_into is None \
-        else torch.from_numpy(accumulate_into.astype(np.float32)).cuda()
-    plan.crystallinity(t.data_ptr(), frames.dtype, n, ld, None if rm is None else rm.data_ptr(),
-                       hm.data_ptr(), mask_box(half), out.data_ptr(), accumulate_into is not None)
-    torch.cuda.synchronize()
-    label = plan.last_kernel()
-    plan.close()
-    return out.cpu().numpy(), label
+# (_cryst_reference, _cryst_run: tests/cryst_ref.py, shared with tests/test_fft_route_kernels_gpu.py)
 
 
 @pytest.mark.gpu
