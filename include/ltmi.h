@@ -686,19 +686,42 @@ int ltmi_comm_all_gather(ltmi_comm *c, const void *send, void *recv, int64_t byt
 int ltmi_comm_all_reduce_sum(ltmi_comm *c, void *buf, int dtype, int64_t n, void *stream);
 
 /* ---- tuning / introspection (bench + tests) ------------------------------------------- */
-/* force a kernel variant for the dense MFMA path (bench / tests only; (0,0,0) = automatic):
- *   mt in {1,2}, waves in {4,8}: the direct-load kernel k_dense_mfma with that tile shape (8 waves:
- *     uint16 tiles only);
- *   mt = 0, waves = 30: the LDS-DMA kernel k_dense_lds as dispatched; 31 / 32: its timing-only
- *     ablations without DMA / without MFMA (results are garbage; uint16 tiles against one column
- *     group only, like 34); 33: padded column groups instead of VALU columns; 34 / 35: one / two
- *     16-frame tiles per wave; 36: float32 tiles of stacks with
- *     2 - 4 column groups on the bf16 x 3 split kernel (ltmi_split.hip); 37: the float32 matrix
- *     instruction also for 1- / 2-byte integer tiles (by default those take exact float16-piece
- *     products, kernel names ending in ",f16"; LTMI_DENSE_F16=0 in the environment: never);
- *   mt = 0, waves = 40 / 41 (sparse handles): as dispatched / the gather kernel k_sell_apply even
- *     if the blocked image exists;
- *   ksplit 0 = auto.  Returns LTMI_E_INVALID for unsupported values. */
+/* the kernel-variant codes of ltmi_masks_set_tuning (passed as `waves` with mt = 0); the numbers are part of the ABI */
+enum ltmi_variant {
+    LTMI_VARIANT_NONE = 0,
+    LTMI_VARIANT_DENSE_DEFAULT = 30,
+    LTMI_VARIANT_DENSE_NO_DMA = 31,
+    LTMI_VARIANT_DENSE_NO_MFMA = 32,
+    LTMI_VARIANT_DENSE_PADDED_GROUPS = 33,
+    LTMI_VARIANT_DENSE_ONE_TILE = 34,
+    LTMI_VARIANT_DENSE_TWO_TILES = 35,
+    LTMI_VARIANT_DENSE_SPLIT_BF16 = 36,
+    LTMI_VARIANT_DENSE_F32_INSTR = 37,
+    LTMI_VARIANT_DENSE_UNFOLDED = 38,
+    LTMI_VARIANT_SPARSE_DEFAULT = 40,
+    LTMI_VARIANT_SPARSE_SELL = 41,
+    LTMI_VARIANT_SPARSE_NO_SCATTER = 42
+};
+/* force a kernel variant of a mask handle (bench / tests only; (0, 0, 0) = automatic).  Two forms:
+ *   mt in {1,2}, waves in {4,8}: the direct-load kernel k_dense_mfma with that tile shape (8 waves: uint16 tiles
+ *     only); mt = 1 on float64 results: the direct-load f64 kernel;
+ *   mt = 0, waves = an ltmi_variant code (the handle then dispatches with mt = waves = 0):
+ *     30  dense stacks as dispatched -- but not the same as 0: every code except 36 disables the bf16 split
+ *         route, also where LTMI_SPLIT=1 asks for it
+ *     31  k_dense_lds / k_dense_fold without the frame DMA: timing only, results are GARBAGE (uint16 tiles against
+ *         one column group only, like 32 and 34)
+ *     32  k_dense_lds / k_dense_fold without the matrix instruction: timing only, results are GARBAGE
+ *     33  padded column groups instead of VALU columns; no column blocks for wide stacks; no row-list launch
+ *     34  one 16-frame tile per wave (uint16 tiles, one column group, no row list)
+ *     35  two 16-frame tiles per wave: 35 is the default shape, so it does what 30 does
+ *     36  float32 tiles of stacks with 2 - 4 column groups on the bf16 x 3 split kernel (ltmi_split.hip)
+ *     37  the float32 matrix instruction also for 1- / 2-byte integer tiles (by default those take exact
+ *         float16-piece products, kernel names ending in ",f16"; LTMI_DENSE_F16=0 in the environment: never)
+ *     38  the unfolded kernels for a stack that has a row-mirror image (ltmi_fold.hip)
+ *     40  sparse stacks as dispatched
+ *     41  the gather kernel k_sell_apply even if a banded, scatter, blocked or label image exists
+ *     42  not the scatter kernel (nor the banded or label image): the blocked image or k_sell_apply
+ *   ksplit: parts of the pixel split, 0 = auto.  Returns LTMI_E_INVALID for anything else. */
 int ltmi_masks_set_tuning(ltmi_masks *m, int mt, int waves, int ksplit);
 /* name of the kernel variant the last ltmi_apply_masks on this handle launched */
 const char *ltmi_masks_last_kernel(const ltmi_masks *m);

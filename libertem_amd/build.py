@@ -40,7 +40,7 @@ def find_hipcc():
 
 def _deps(src):
     deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'ltmi_common.h'), os.path.join(CSRC, 'ltmi_tiles.h'),
-            header_path(),
+            os.path.join(CSRC, 'ltmi_switches.h'), os.path.join(CSRC, 'ltmi_tuning.h'), header_path(),
             os.path.join(CSRC, 'ltmi_scatter_loop.inc') if src == 'ltmi_scatter.hip' else '',
             os.path.abspath(__file__)]
     return [d for d in deps if os.path.exists(d)]

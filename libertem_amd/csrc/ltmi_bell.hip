@@ -1073,7 +1073,7 @@ static BellImage *build_image(const int64_t *indptr, const int64_t *indices, con
         // ---- per pass: which segments hold entries, how they are grouped into chunks
         std::vector<int> active, active_off(n_pass + 1, 0);     // active: [chunk][NSEG] segment numbers
         std::vector<int> chunk_of_seg((size_t)n_pass * n_seg, -1), slot_of_seg((size_t)n_pass * n_seg, 0);
-        const bool natural = getenv("LTMI_BELL_NATURAL_CHUNKS") != nullptr;     // experiments: no planning
+        const bool natural = switch_set<LTMI_BELL_NATURAL_CHUNKS>();     // experiments: no planning
         for (int ps = 0; ps < n_pass; ++ps) {
             const int64_t g_lo = (int64_t)ps * GPP;
             const int n_local = (int)std::min<int64_t>(GPP, n_groups - g_lo);
@@ -1345,7 +1345,7 @@ void *bell_build(const int64_t *indptr, const int64_t *indices, const float *val
         for (int64_t e = 0; e < indptr[n_px]; ++e) per_mask[(size_t)indices[e]]++;
         for (int64_t v : per_mask) b->max_col_entries = std::max(b->max_col_entries, v);
     }
-    const char *off = getenv("LTMI_BELL_F16");
+    const char *off = switch_text<LTMI_BELL_F16>();
     if (off && atoi(off) == 0) return b;
     const int64_t n_cols = n_masks * nc;
     std::vector<float> amax((size_t)n_cols, 0.f);
@@ -1435,8 +1435,7 @@ static int launch_bell_t(ltmi_masks *m, BellImage *b, const MaskCall &call, int 
         set[m->device & 15] = true;
     }
     dim3 grid((unsigned)((call.n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
-    const char *abl = getenv("LTMI_BELL_ABLATE");    // 1: no frame DMA, 2: no records (bench only)
-    const int ablate = abl ? atoi(abl) : 0;
+    const int ablate = switch_int<LTMI_BELL_ABLATE>(0);     // 1: no frame DMA, 2: no records (bench only)
     unsigned long long *prof = nullptr;
 #ifdef BE_PROF
     static unsigned long long *prof_dev = nullptr;
@@ -1489,8 +1488,7 @@ static int launch_bell_flat(ltmi_masks *m, BellImage *b, const MaskCall &call, i
         set[m->device & 15] = true;
     }
     dim3 grid((unsigned)((call.n_frames + C::FB - 1) / C::FB), (unsigned)b->n_pass);
-    const char *abl = getenv("LTMI_BELL_ABLATE");
-    const int ablate = abl ? atoi(abl) : 0;
+    const int ablate = switch_int<LTMI_BELL_ABLATE>(0);
     hipLaunchKernelGGL(kern, grid, dim3(BE_SETS * 64), LDS, call.stream, tile, call.ld_tile, call.n_frames, m->n_px,
                        (const uint32_t *)b->stream, (const int64_t *)b->stream_off,
                        (const uint32_t *)b->ctrl, (const int64_t *)b->ctrl_off, (const int *)b->n_rec,
@@ -1518,7 +1516,7 @@ static int launch_bell_flat(ltmi_masks *m, BellImage *b, const MaskCall &call, i
 template <typename T>
 static int launch_bell(ltmi_masks *m, BellImage *b, const MaskCall &call, int n_cols) {
     constexpr int LO = sizeof(T) == 4 ? 1 : 2, HI = 2 * LO;
-    static const int forced = getenv("LTMI_BELL_TILES") ? atoi(getenv("LTMI_BELL_TILES")) : 0;
+    const int forced = switch_int<LTMI_BELL_TILES>(0);
     auto rounds = [&](int tl) { return (double)(((call.n_frames + 16 * tl - 1) / (16 * tl) + 255) / 256); };
     const bool hi = forced ? forced == HI : rounds(HI) * 1.7 < rounds(LO);
     // k_bell_apply with four tiles has one accumulation level only: not for columns of more than 2048 stored values

@@ -86,8 +86,7 @@ struct CopyPool {
     static const std::vector<cpu_set_t> &domains() {
         static const std::vector<cpu_set_t> d = [] {
             std::vector<cpu_set_t> out;
-            const char *e = getenv("LTMI_COPY_SPREAD");
-            if (e && e[0] == '0') return out;
+            if (ltmi::switch_is<ltmi::LTMI_COPY_SPREAD>('0')) return out;
             cpu_set_t allowed;
             CPU_ZERO(&allowed);
             if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return out;
@@ -225,6 +224,5 @@ static void ltmi_abort_backtrace(int sig) {
     raise(sig);
 }
 __attribute__((constructor)) static void ltmi_debug_init() {
-    const char *e = getenv("LTMI_ABORT_BACKTRACE");
-    if (e && e[0] == '1') signal(SIGABRT, ltmi_abort_backtrace);
+    if (ltmi::switch_is<ltmi::LTMI_ABORT_BACKTRACE>('1')) signal(SIGABRT, ltmi_abort_backtrace);
 }

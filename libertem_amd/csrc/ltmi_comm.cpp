@@ -81,7 +81,7 @@ static Rccl *rccl() {
         r.was_loaded = r.lib != nullptr;
     }
     if (!r.lib) {
-        const char *env = getenv("LTMI_RCCL_LIB");
+        const char *env = ltmi::switch_text<ltmi::LTMI_RCCL_LIB>();
         const char *names[] = {env ? env : "librccl.so.1", "librccl.so.1", "librccl.so",
                                "/opt/rocm/lib/librccl.so.1"};
         for (const char *n : names) {

@@ -5,12 +5,15 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <string.h>
 #include <string>
 #include <algorithm>
 #include <type_traits>
 #include <utility>
 #include <vector>
 #include "../../include/ltmi.h"
+#include "ltmi_switches.h"
+#include "ltmi_tuning.h"
 
 namespace ltmi {
 
@@ -37,7 +40,7 @@ void set_error(const char *fmt, ...);
 // counts, e.g. 515 x 515 detectors) take the same vectorised kernels.  LTMI_ALIGNED_DMA_ONLY=1 in the
 // environment restores the conservative dispatch (vector paths for 16-B aligned rows only).
 static inline bool vector_loads_ok(const void *tile, int64_t ld_elems, size_t elem) {
-    static const bool aligned_only = getenv("LTMI_ALIGNED_DMA_ONLY") != nullptr;
+    const bool aligned_only = switch_set<LTMI_ALIGNED_DMA_ONLY>();
     if ((((uintptr_t)tile) % 16 == 0) && ((ld_elems * (int64_t)elem) % 16 == 0)) return true;
     return !aligned_only && ((uintptr_t)tile) % elem == 0;
 }
@@ -330,7 +333,7 @@ struct ltmi_masks {
     void *shift_cache = nullptr;   // ltmi_dense.hip: images of the stack shifted by (dy, dx)
     void *fold = nullptr;          // ltmi_fold.hip: image folded about a mirror of the detector rows (ltmi_masks_set_sig_shape)
     ltmi::DevBuf<void> partials;  // arrival counters, then the partial sums of a K split (ltmi_dense.hip)
-    int tune_mt = 0, tune_waves = 0, tune_ksplit = 0, tune_ksplit_ring = 0;
+    ltmi::Tuning tune;       // ltmi_masks_set_tuning (ltmi_tuning.h)
     // kind 0 and 1
     ltmi::DevBuf<void> gmasks;    // (n_masks, n_px) of the accumulate type
     // ltmi_apply_masks_csr: the stack again pixel-major, [n_px][m_pad_px] of float / double, built on first use
@@ -349,3 +352,14 @@ struct ltmi_masks {
     bool last_exact = false;               // the last product ran on a kernel that multiplies stored entries only
     char last_kernel[128] = {0};
 };
+
+namespace ltmi {
+// what a later stage did to the product of the kernel that `last_kernel` names: " +nf", " exact-int", " shifted, ..."
+__attribute__((format(printf, 2, 3))) static inline void append_kernel_note(ltmi_masks *m, const char *fmt, ...) {
+    const size_t len = strlen(m->last_kernel);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, fmt, ap);
+    va_end(ap);
+}
+}  // namespace ltmi

@@ -589,7 +589,7 @@ static int launch_fused_w(const void *tile, int64_t ld, int64_t n_frames, const 
                           int accumulate, int n_cu, hipStream_t stream) {
     auto kern = real_mask ? k_cryst_fused<T, true, WAVES> : k_cryst_fused<T, false, WAVES>;
     if constexpr (std::is_same<T, uint16_t>::value && WAVES == 16) {
-        static const int abl = getenv("LTMI_CRYST_ABLATE") ? atoi(getenv("LTMI_CRYST_ABLATE")) : 0;
+        const int abl = switch_int<LTMI_CRYST_ABLATE>(0);
         if (real_mask && abl == 1) kern = k_cryst_fused<T, true, WAVES, 1>;
         if (real_mask && abl == 2) kern = k_cryst_fused<T, true, WAVES, 2>;
         if (real_mask && abl == 3) kern = k_cryst_fused<T, true, WAVES, 3>;
@@ -601,7 +601,7 @@ static int launch_fused_w(const void *tile, int64_t ld, int64_t n_frames, const 
     int device = 0;
     LTMI_HIP(hipGetDevice(&device));
     static bool attr_set[16][2] = {{false}};          // per device (and per pixel type: one copy per T)
-    if (!attr_set[device & 15][real_mask ? 1 : 0] || getenv("LTMI_CRYST_ABLATE")) {
+    if (!attr_set[device & 15][real_mask ? 1 : 0] || switch_set<LTMI_CRYST_ABLATE>()) {
         LTMI_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      CF_LDS_MAX));
         attr_set[device & 15][real_mask ? 1 : 0] = true;
@@ -615,12 +615,7 @@ static int launch_fused_w(const void *tile, int64_t ld, int64_t n_frames, const 
 }
 
 static int cf_waves() {                               // LTMI_CRYST_WAVES=8 / 16 (measurement switch)
-    static int v = 0;
-    if (!v) {
-        const char *env = getenv("LTMI_CRYST_WAVES");
-        v = env && atoi(env) == 8 ? 8 : 16;
-    }
-    return v;
+    return switch_int<LTMI_CRYST_WAVES>(0) == 8 ? 8 : 16;
 }
 
 template <typename T>
@@ -1190,7 +1185,8 @@ static int launch_rows(const void *tile, int64_t ld, int64_t n_frames, const flo
 
 // frames per pass of the workspace: LTMI_CRYST_PASS_MIB (measurement switch) caps the bytes a pass writes and reads back
 static int64_t cryst_pass_frames(int64_t gbuf_frames, int64_t bytes_per_frame, int n_cu) {
-    static const long mib = [] { const char *e = getenv("LTMI_CRYST_PASS_MIB"); return e ? atol(e) : 0L; }();
+    const char *e = switch_text<LTMI_CRYST_PASS_MIB>();
+    const long mib = e ? atol(e) : 0L;
     if (mib <= 0) return gbuf_frames;
     const int64_t n = std::max<int64_t>(1, ((int64_t)mib << 20) / bytes_per_frame);
     return std::min(gbuf_frames, n);

@@ -1540,7 +1540,7 @@ extern "C" int ltmi_masks_create_dense(int device, const void *masks_host, int r
         const bool want_h2 = m->ng > 1 && m->img2 != nullptr;
         const bool want_h3 = m->img3 != nullptr && m->ng3 == 3 && m->ne3 == 0;
         if (e == hipSuccess && (want_h1 || want_h2 || want_h3)) {
-            const char *off = getenv("LTMI_DENSE_F16");
+            const char *off = switch_text<LTMI_DENSE_F16>();
             const float *hm = (const float *)masks_host;      // (n_masks, n_px, cpm) float32 on the host
             std::vector<float> amax((size_t)m->n_cols, 0.f);
             bool finite = !(off && atoi(off) == 0);
@@ -1698,30 +1698,12 @@ extern "C" int ltmi_masks_kind(const ltmi_masks *m, int *kind) {
 
 extern "C" int ltmi_masks_set_tuning(ltmi_masks *m, int mt, int waves, int ksplit) {
     if (!m) LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_set_tuning: null handle");
-    if (mt == 0 && ((waves >= 30 && waves <= 38) || (waves >= 40 && waves <= 42))) {
-        // k_dense_lds: 30 = as dispatched, 31 / 32 = timing-only ablations (no DMA / no MFMA),
-        // 34 / 35 = one / two frame tiles per wave; 36 = k_dense_split (float32 frames, ltmi_split.hip);
-        // 37 = the float32 matrix instruction also where the exact float16 products (X16) apply;
-        // 38 = the unfolded kernels for a stack that has a row-mirror image (ltmi_fold.hip);
-        // sparse stacks: 40 = as dispatched, 41 = SELL kernel even if a blocked / scatter image exists,
-        // 42 = not the scatter kernel (blocked image or SELL)
-        m->tune_mt = 0;
-        m->tune_waves = 0;
-        m->tune_ksplit = ksplit;
-        m->tune_ksplit_ring = waves;
-    } else {
-        if (!(mt == 0 || mt == 1 || mt == 2) || !(waves == 0 || waves == 4 || waves == 8) || ksplit < 0)
-            LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_set_tuning: unsupported (mt=%d waves=%d ksplit=%d)",
-                      mt, waves, ksplit);
-        m->tune_mt = mt;
-        m->tune_waves = waves;
-        m->tune_ksplit = ksplit;
-        m->tune_ksplit_ring = 0;
-    }
+    if (m->tune.set(mt, waves, ksplit) != LTMI_OK)         // (the codes: enum ltmi_variant, include/ltmi.h)
+        LTMI_FAIL(LTMI_E_INVALID, "ltmi_masks_set_tuning: unsupported (mt=%d waves=%d ksplit=%d)", mt, waves, ksplit);
     // (the column blocks of a wide stack run only while mt = waves = 0: the split and the code are theirs too)
     for (ltmi_masks *b : m->blocks) {
-        b->tune_ksplit = m->tune_ksplit;
-        b->tune_ksplit_ring = m->tune_ksplit_ring;
+        b->tune.ksplit = m->tune.ksplit;
+        b->tune.variant = m->tune.variant;
     }
     return LTMI_OK;
 }
@@ -1752,7 +1734,7 @@ static inline int *partial_counters(const ltmi_masks *m, int64_t n_blocks) {
     // 45 / 114 / 167 us.  The ~20 us it costs whatever the split are the device-scope fences: partials
     // written under one XCD's L2 must be made visible to a workgroup on another XCD (L2 write-back +
     // invalidate inside the kernel), which the kernel boundary of the second launch does once for all.
-    static const bool off = getenv("LTMI_KSPLIT_FUSED") == nullptr;
+    const bool off = !switch_set<LTMI_KSPLIT_FUSED>();
     return (m->partials && !off && n_blocks * (int64_t)sizeof(int) <= (int64_t)KCOUNT_BYTES)
                ? (int *)m->partials.get() : nullptr;
 }
@@ -1811,9 +1793,7 @@ static LdsKernel<T> lds_kernel() {
 // handle, or LTMI_DENSE_F32_INSTR=1 in the environment (read per launch: bench.py times both arithmetics
 // through Context.run_udf with the same cached handle)
 static inline bool f32_instruction_only(const ltmi_masks *m) {
-    if (m->tune_ksplit_ring == 37) return true;
-    const char *e = getenv("LTMI_DENSE_F32_INSTR");
-    return e && e[0] == '1';
+    return m->tune.f32_instruction() || switch_is<LTMI_DENSE_F32_INSTR>('1');
 }
 
 // the parts of a pixel-split launch: mask slots in turn (negative: k_dense_lds) or a contiguous range each
@@ -1823,14 +1803,14 @@ static inline bool f32_instruction_only(const ltmi_masks *m) {
 // frames and 48 columns: no difference (scripts/r5_run18.sh, r5_run19.sh).  In turn for 8, 16, 32, 64 parts.
 // LTMI_KSPLIT_STRIDED = 0: never, v > 0: runs of 2^(v-1) slots whatever the number of parts.
 static inline int ksplit_order(int ksplit) {
-    static const int forced = getenv("LTMI_KSPLIT_STRIDED") ? atoi(getenv("LTMI_KSPLIT_STRIDED")) : -1;
+    const int forced = switch_int<LTMI_KSPLIT_STRIDED>(-1);
     if (ksplit <= 1 || forced == 0) return ksplit;
     if (forced > 0) return -(ksplit | ((forced - 1) << 16));
     return (ksplit >= 8 && (ksplit & (ksplit - 1)) == 0) ? -(ksplit | (2 << 16)) : ksplit;
 }
 
 static inline int lds_tiles(const ltmi_masks *m) {
-    return m->tune_ksplit_ring == 34 ? 1 : 2;
+    return m->tune.one_tile() ? 1 : 2;
 }
 
 // what the launches of k_dense_lds over a whole tile share: LDS size of the kernel (once per device and variant:
@@ -1845,7 +1825,7 @@ static int launch_lds_kernel(ltmi_masks *m, const MaskCall &call, LdsKernel<T> k
         *attr_set = true;
     }
     const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, n_slots);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, n_slots)), n_slots);
     if (ksplit > 1) {
@@ -1875,7 +1855,7 @@ static int launch_lds_kernel(ltmi_masks *m, const MaskCall &call, LdsKernel<T> k
 template <typename T, int NG, int TILES>
 static int launch_lds_ng_t(ltmi_masks *m, const MaskCall &call) {
     using CFG = LdsCfg<NG, 0, TILES>;
-    const int abl = m->tune_ksplit_ring == 31 ? 2 : (m->tune_ksplit_ring == 32 ? 1 : 0);
+    const int abl = m->tune.ablation();
     LdsKernel<T> kern = abl == 2 ? lds_kernel<T, NG, 2, 0, 0, TILES>()
                                  : (abl == 1 ? lds_kernel<T, NG, 1, 0, 0, TILES>()
                                              : lds_kernel<T, NG, 0, 0, 0, TILES>());
@@ -1892,7 +1872,7 @@ static int launch_lds_ng_t(ltmi_masks *m, const MaskCall &call) {
     }
     if (!kern)
         LTMI_FAIL(LTMI_E_DTYPE, "k_dense_lds<%s, NG=%d>: tuning code %d (ablations / one tile per wave) is built for "
-                  "uint16 tiles and one column group only", typeid(T).name(), NG, m->tune_ksplit_ring);
+                  "uint16 tiles and one column group only", typeid(T).name(), NG, m->tune.variant);
     static bool attr_set[16][8] = {{false}};
     const int variant = (rows ? 3 : abl) + (x16 ? 4 : 0);
     const float *img = x16 ? (NG == 1 ? m->img_h : m->img2_h) : (NG == 1 ? m->img : m->img2);
@@ -1928,7 +1908,7 @@ static int launch_lds_extras(ltmi_masks *m, const MaskCall &call) {
     }
     if (!kern)
         LTMI_FAIL(LTMI_E_DTYPE, "k_dense_lds<%s, NG=%d + %d VALU columns>: variant not built (tuning code %d)",
-                  typeid(T).name(), NG, NE, m->tune_ksplit_ring);
+                  typeid(T).name(), NG, NE, m->tune.variant);
     static bool attr_set[16][4] = {{false}};
     const int variant = (rows ? 1 : 0) + (x16 ? 2 : 0);
     char name[96];
@@ -1983,7 +1963,7 @@ static int launch_lds(ltmi_masks *m, const MaskCall &call) {
         bool x16_group = false;
         if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value)
             x16_group = m->img_h != nullptr && !f32_instruction_only(m);
-        if (m->img3 && m->ng3 == 0 && m->tune_ksplit_ring != 33 && !x16_group) {
+        if (m->img3 && m->ng3 == 0 && !m->tune.padded_groups() && !x16_group) {
             if (m->ne3 == 2) return launch_lds_extras<T, 0, 2>(m, call);
             return launch_lds_extras<T, 0, 4>(m, call);
         }
@@ -1994,7 +1974,7 @@ static int launch_lds(ltmi_masks *m, const MaskCall &call) {
     bool x16_padded = false;
     if constexpr (sizeof(T) <= 2 && std::is_integral<T>::value)
         x16_padded = m->ne3 > 0 && m->img2_h != nullptr && !f32_instruction_only(m);
-    if (m->img3 && m->ng3 > 0 && m->tune_ksplit_ring != 33 && !x16_padded) {   // 33: force the padded-group kernel (bench)
+    if (m->img3 && m->ng3 > 0 && !m->tune.padded_groups() && !x16_padded) {   // 33: force the padded-group kernel (bench)
 #define LTMI_EXTRAS(NG_, NE_) \
     if (m->ng3 == NG_ && m->ne3 == NE_) return launch_lds_extras<T, NG_, NE_>(m, call);
         LTMI_EXTRAS(1, 2)
@@ -2200,10 +2180,9 @@ static int launch_mfma(ltmi_masks *m, const MaskCall &call) {
         // opt-in (LTMI_SPLIT=1 or tuning code 36): float32 frames against two or more column groups
         // as bf16 pieces on the bf16 matrix cores (ltmi_split.hip; measured slower than k_dense_lds
         // on C5, profiles/r03_split.txt, hence not the default).  The image is made on first use.
-        if (ltmi::split_selected(m->tune_ksplit_ring == 36) && m->blocks.empty() && !call.rows &&
+        if (ltmi::split_selected(m->tune.split_forced()) && m->blocks.empty() && !call.rows &&
             m->result_dtype != LTMI_F64 && ltmi::split_wanted(m->n_cols, m->n_px) &&
-            vector_loads_ok(tile, ld, sizeof(T)) && m->tune_mt == 0 && m->tune_waves == 0 &&
-            (m->tune_ksplit_ring == 0 || m->tune_ksplit_ring == 36)) {
+            vector_loads_ok(tile, ld, sizeof(T)) && m->tune.dispatched_shape() && m->tune.split_eligible()) {
             if (!m->split) {
                 const int cpm = (m->result_dtype == LTMI_C64) ? 2 : 1;
                 const int rcs = ltmi::split_create(m->device, (const float *)m->gmasks.get(), m->n_masks, cpm,
@@ -2213,15 +2192,14 @@ static int launch_mfma(ltmi_masks *m, const MaskCall &call) {
             return ltmi::split_apply(m, m->split, call);
         }
     }
-    if (vector_loads_ok(tile, ld, sizeof(T)) && m->tune_mt == 0 && m->tune_waves == 0 &&
-        lds_kernel_applies<T>(m))
+    if (vector_loads_ok(tile, ld, sizeof(T)) && m->tune.dispatched_shape() && lds_kernel_applies<T>(m))
         return launch_lds<T>(m, call);
-    int waves = m->tune_waves ? m->tune_waves : 4;
-    int mt = m->tune_mt ? m->tune_mt : (n_frames >= 256 * waves * 32 ? 2 : 1);
+    int waves = m->tune.waves ? m->tune.waves : 4;
+    int mt = m->tune.mt ? m->tune.mt : (n_frames >= 256 * waves * 32 ? 2 : 1);
     if (m->ng == 4) { mt = 1; }   // keep the accumulator/LDS budget in check
     const int64_t gx = (n_frames + waves * mt * 16 - 1) / (waves * mt * 16);
     const int64_t gz = m->n_groups / m->ng;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) {
         // split K only when the frame/column tiling alone leaves CUs idle (< 2 workgroups per CU):
         // measured on C2, 512 workgroups without a split beat 1024 with one (profiles/r01_*)
@@ -2386,7 +2364,7 @@ int ltmi::apply_masks_unguarded(ltmi_masks *m, const MaskCall &call) {
     m->last_exact = false;
     if (m->kind == 2) return ltmi::csr_apply(m, call);
     if (m->kind == 0 && mfma_tile_dtype(tile_dtype) && !m->blocks.empty() &&
-        m->tune_mt == 0 && m->tune_waves == 0 && m->tune_ksplit_ring != 33) {
+        m->tune.dispatched_shape() && !m->tune.padded_groups()) {
         const size_t elem = (size_t)dtype_size(m->result_dtype);
         for (size_t b = 0; b < m->blocks.size(); ++b) {
             MaskCall block = call;
@@ -2455,8 +2433,8 @@ extern "C" int ltmi_apply_masks_rows(ltmi_masks *m, const void *tile, int tile_d
         // float64 / complex128 results: the f64 LDS-DMA kernel reads frames through the row list
         return product();
     }
-    if (m->kind != 0 || !mfma_tile_dtype(tile_dtype) || m->tune_mt != 0 ||
-        m->tune_waves != 0 || m->tune_ksplit_ring == 33 || n_rows >= (1ll << 31) ||
+    if (m->kind != 0 || !mfma_tile_dtype(tile_dtype) || !m->tune.dispatched_shape() ||
+        m->tune.padded_groups() || n_rows >= (1ll << 31) ||
         !vector_loads_ok(tile, ld_tile, (size_t)dtype_size(tile_dtype)))
         return LTMI_OK;
     auto lds_ok = [&](const ltmi_masks *h) {
@@ -2561,10 +2539,7 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
         bool ok = false;
         const int rc = ltmi::dense64_apply(m, c->images64[keys[0]], call, &ok);
         if (rc != LTMI_OK) return rc;
-        if (ok) {
-            const size_t len = strlen(m->last_kernel);
-            snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " shifted, 1 group");
-        }
+        if (ok) append_kernel_note(m, " shifted, 1 group");
         *handled = ok;
         return LTMI_OK;
     }
@@ -2622,10 +2597,7 @@ static int shifted64(ltmi_masks *m, const MaskCall &call, int sig_h, int sig_w, 
         }
         LTMI_HIP(hipGetLastError());
     }
-    {
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " shifted, %zu groups", keys.size());
-    }
+    append_kernel_note(m, " shifted, %zu groups", keys.size());
     *handled = true;
     return LTMI_OK;
 }
@@ -2729,8 +2701,7 @@ extern "C" int ltmi_apply_masks_shifted_host(ltmi_masks *m, const void *tile, in
         const ShiftCtx redo{shifts_dev, sig_h, sig_w, listed, n_listed};
         rc = apply_generic(m, MaskCall{tile, tile_dtype, n_frames, ld_tile, target, ld_t, 0, stream}, &redo);
         if (rc != LTMI_OK) return rc;
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
+        append_kernel_note(m, " +nf");
         return ltmi::guard_deliver(m, out, ld_out, n_frames, accumulate, stream);
     };
     if (lds_route) {

@@ -557,7 +557,7 @@ static int launch64_lds(ltmi_masks *m, const double *img64, const MaskCall &call
     }
     const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
     const int64_t gz = m->n_groups64;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, m->n_chunks64);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, m->n_chunks64)), m->n_chunks64);
     if (ksplit > 1) {
@@ -605,7 +605,7 @@ bool dense64_rows_ok(const ltmi_masks *m, const void *tile, int tile_dtype, int6
     if (int_result ? !int_product_is_exact(m, tile_dtype)
                    : (m->result_dtype != LTMI_F64 && m->result_dtype != LTMI_C128)) return false;
     if (tile_dtype == LTMI_C64 || tile_dtype == LTMI_C128 || dtype_size(tile_dtype) == 0) return false;
-    return m->tune_mt != 1 && m->n_px >= KC64 &&
+    return m->tune.mt != 1 && m->n_px >= KC64 &&
            vector_loads_ok(tile, ld, (size_t)dtype_size(tile_dtype));
 }
 
@@ -613,16 +613,16 @@ template <typename T>
 static int launch64(ltmi_masks *m, const double *img64, const MaskCall &call) {
     const T *tile = (const T *)call.tile;
     double *out = (double *)call.out;
-    // tune_mt == 1 (ltmi_masks_set_tuning): force the direct-load kernel (bench comparison)
+    // tune.mt == 1 (ltmi_masks_set_tuning): force the direct-load kernel (bench comparison)
     // (rows need not be 16-B aligned: LDS-DMA reads from any element-aligned address)
-    if (m->tune_mt != 1 && m->n_px >= KC64 && vector_loads_ok(tile, call.ld_tile, sizeof(T)))
+    if (m->tune.mt != 1 && m->n_px >= KC64 && vector_loads_ok(tile, call.ld_tile, sizeof(T)))
         return launch64_lds<T>(m, img64, call);
     if (call.rows) LTMI_FAIL(LTMI_E_INVALID, "k_dense_mfma_f64 does not take a row list");
     constexpr int WAVES = 4;
     const bool vec = (((uintptr_t)tile) % (4 * sizeof(T)) == 0) && (call.ld_tile % 4 == 0);
     const int64_t gx = (call.n_frames + WAVES * 16 - 1) / (WAVES * 16);
     const int64_t gz = m->n_groups64;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) {
         ksplit = 1;
         if (gx * gz < 512)
@@ -708,8 +708,7 @@ int dense64_apply(ltmi_masks *m, const double *img64, const MaskCall &call, bool
             default: hipLaunchKernelGGL(k_f64_to_int<uint64_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint64_t *)out, ld_out, accumulate); break;
         }
         LTMI_HIP(hipGetLastError());
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " exact-int");
+        append_kernel_note(m, " exact-int");
     }
     *handled = true;
     return LTMI_OK;

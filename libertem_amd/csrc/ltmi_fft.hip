@@ -291,8 +291,7 @@ extern "C" int ltmi_fft_plan_create(int device, int sig_h, int sig_w, int max_ba
     p->batch = max_batch;
     hipError_t e = hipSuccess;
     if (cryst_fused_shape(sig_h, sig_w)) {
-        const char *env = getenv("LTMI_FFT_FUSED");
-        p->fused_ok = !(env && env[0] == '0');
+        p->fused_ok = !switch_is<LTMI_FFT_FUSED>('0');
         e = p->mask_t.alloc((size_t)cryst_fused_workspace_floats(sig_h, sig_w));
         if (e == hipSuccess) e = hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, device);
         if (e != hipSuccess) {
@@ -412,7 +411,7 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
         }
     }
     if (p->fused_ok && (corr.dark || corr.gain || corr.n_excl > 0) &&
-        cryst_corr_takes(p->h, p->w, n_cols, tile_dtype, corr.n_excl) && !getenv("LTMI_CRYST_CORR_PASS")) {
+        cryst_corr_takes(p->h, p->w, n_cols, tile_dtype, corr.n_excl) && !switch_set<LTMI_CRYST_CORR_PASS>()) {
         // dark / gain / dead-pixel patches inside the row stage of the fused kernels -- ONE pass over the raw pixels
         // (round 5; LTMI_CRYST_CORR_PASS=1 keeps the conversion pass: tests, bench).  Frames in chunks whose patch
         // values fit 64 MiB.

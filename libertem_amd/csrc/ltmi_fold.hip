@@ -935,7 +935,7 @@ void ltmi::fold_destroy(ltmi_masks *m) {
 // that saves matrix work.  Not an error when there is none (the handle then works as before).
 int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
     fold_destroy(m);
-    const char *off = getenv("LTMI_DENSE_FOLD");
+    const char *off = switch_text<LTMI_DENSE_FOLD>();
     if (off && atoi(off) == 0) return LTMI_OK;
     if (m->kind != 0 || !m->gmasks || (int64_t)sig_h * sig_w != m->n_px || sig_h < 4) return LTMI_OK;
     if (sig_w % FD_KB != 0 || m->n_cols > 4 * GROUP) return LTMI_OK;
@@ -1019,7 +1019,7 @@ int ltmi::fold_create(ltmi_masks *m, int sig_h, int sig_w) {
 
 bool ltmi::fold_takes(const ltmi_masks *m, const float *tile, int64_t ld) {
     const FoldImage *f = (const FoldImage *)m->fold;
-    if (!f || m->tune_ksplit_ring == 38) return false;                  // tuning 38: the unfolded kernels (bench, tests)
+    if (!f || m->tune.unfolded()) return false;                  // tuning 38: the unfolded kernels (bench, tests)
     return ((uintptr_t)tile % 16 == 0) && (ld * 4) % 16 == 0;
 }
 
@@ -1028,7 +1028,7 @@ static int launch_fold_t(ltmi_masks *m, const MaskCall &call) {
     const float *tile = (const float *)call.tile;
     float *out = (float *)call.out;
     const FoldImage *f = (const FoldImage *)m->fold;
-    const int abl = m->tune_ksplit_ring == 31 ? 2 : (m->tune_ksplit_ring == 32 ? 1 : 0);
+    const int abl = m->tune.ablation();
     auto kern = abl == 2 ? k_dense_fold<NGE, NGO, 2> : (abl == 1 ? k_dense_fold<NGE, NGO, 1> : k_dense_fold<NGE, NGO, 0>);
     constexpr int LDS = ltmi::fold_lds_bytes(NGE + NGO);
     static bool attr_set[16][3] = {{false}};
@@ -1037,7 +1037,7 @@ static int launch_fold_t(ltmi_masks *m, const MaskCall &call) {
         attr_set[m->device & 15][abl] = true;
     }
     const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx, f->n_stages);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, f->n_stages)), f->n_stages);
     if (ksplit > 1) {
@@ -1045,12 +1045,11 @@ static int launch_fold_t(ltmi_masks *m, const MaskCall &call) {
         if (rc != LTMI_OK) return rc;
     }
     dim3 grid((unsigned)gx, (unsigned)ksplit);
-    static const int turn_env = getenv("LTMI_FOLD_TURN") ? atoi(getenv("LTMI_FOLD_TURN")) : -1;
+    const int turn_env = switch_int<LTMI_FOLD_TURN>(-1);
     const bool in_turn = ksplit > 1 && (turn_env >= 0 ? turn_env != 0 : FOLD_TURN_DEFAULT);
     // two waves per SIMD (k_dense_fold8): stacks of 2 or 4 column groups; measured 3 - 5 % SLOWER than the pipelined
     // one-wave-per-SIMD kernel on C5 (profiles/r06_fold.txt), kept as a measurement switch: LTMI_FOLD_WAVES=8
-    const char *fw = getenv("LTMI_FOLD_WAVES");               // (read per launch: tests and benches switch it)
-    const int want_waves = fw ? atoi(fw) : 0;
+    const int want_waves = switch_int<LTMI_FOLD_WAVES>(0);    // (read per launch: tests and benches switch it)
     bool eight = false;
     if constexpr ((NGE + NGO) % 2 == 0) eight = abl == 0 && (want_waves == 8 || (want_waves == 0 && FOLD8_DEFAULT));
     if (eight) {
@@ -1097,7 +1096,7 @@ int ltmi::launch_fold(ltmi_masks *m, const MaskCall &call) {
 // ---- 2-byte pixels ------------------------------------------------------------------------------------------------
 bool ltmi::fold_takes16(ltmi_masks *m, const void *tile, int64_t ld, int px_bytes) {
     FoldImage *f = (FoldImage *)m->fold;
-    if (!f || m->tune_ksplit_ring == 38 || f->img16_failed) return false;
+    if (!f || m->tune.unfolded() || f->img16_failed) return false;
     if (f->sig_w % FD16_KB != 0 || ((uintptr_t)tile % 16 != 0) || (ld * px_bytes) % 16 != 0) return false;
     if (!f->img16) {
         // built on the first 2-byte tile (a stack that only ever sees float32 frames does not pay for it)
@@ -1137,7 +1136,7 @@ static int launch_fold16_t(ltmi_masks *m, const MaskCall &call) {
         attr_set[m->device & 15] = true;
     }
     const int64_t gx = (call.n_frames + FD_WG_ROWS - 1) / FD_WG_ROWS;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx, f->n_stages16);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, f->n_stages16)), f->n_stages16);
     if (ksplit > 1) {
@@ -1216,7 +1215,7 @@ struct BandImage {
 
 ltmi::KeptCsr *ltmi::band_keep_csr(const int64_t *indptr, const int64_t *indices, const float *vals, int nc,
                                    int64_t n_px, int64_t n_masks) {
-    const char *off = getenv("LTMI_SPARSE_BAND");
+    const char *off = switch_text<LTMI_SPARSE_BAND>();
     if (off && atoi(off) == 0) return nullptr;
     const int64_t nnz = indptr[n_px];
     if (nnz <= 0 || n_masks * nc < 2 * GROUP || n_masks >= (1 << 30)) return nullptr;
@@ -1262,7 +1261,7 @@ void ltmi::band_destroy(void *band) { delete (BandImage *)band; }
 // `other_macs`: padded multiply-adds per frame of the kernel that would run instead (blocked image), 0: unknown.
 // Returns the image or nullptr (no mirror, no common supports, not worth it, no memory: the other kernels serve).
 static void *band_no(int why) {
-    if (getenv("LTMI_BAND_DEBUG")) fprintf(stderr, "band_build: no image (exit %d)\n", why);
+    if (switch_set<LTMI_BAND_DEBUG>()) fprintf(stderr, "band_build: no image (exit %d)\n", why);
     return nullptr;
 }
 
@@ -1476,7 +1475,7 @@ void *ltmi::band_build(const KeptCsr *k, int sig_h, int sig_w, double other_macs
         const double reread = (double)total / (double)n_slots;
         const double t_band = std::max(band_macs * 2. / 130e12, reread * (double)k->n_px * 4. / 6.5e12);
         const double t_other = other_macs > 0. ? other_macs * 2. / 60e12 : (double)nnz * nc / 10e12;
-        const char *force = getenv("LTMI_SPARSE_BAND");
+        const char *force = switch_text<LTMI_SPARSE_BAND>();
         if (!(force && atoi(force) == 1) && !(t_band < 0.8 * t_other)) return band_no(5);
         if (total == 0 || total > (size_t)INT32_MAX / 2) return band_no(6);
 
@@ -1589,7 +1588,7 @@ void *ltmi::band_build(const KeptCsr *k, int sig_h, int sig_w, double other_macs
 
 bool ltmi::band_takes(void *band, const ltmi_masks *m, const void *tile, int tile_dtype, int64_t ld) {
     BandImage *b = (BandImage *)band;
-    if (!b || m->tune_ksplit_ring == 41 || m->tune_ksplit_ring == 42) return false;
+    if (!b || m->tune.no_band()) return false;
     if ((uintptr_t)tile % 16 != 0) return false;
     if (tile_dtype == LTMI_F32) return (ld * 4) % 16 == 0;
     const int px_bytes = (tile_dtype == LTMI_U8 || tile_dtype == LTMI_I8)
@@ -1628,7 +1627,7 @@ bool ltmi::band_takes(void *band, const ltmi_masks *m, const void *tile, int til
 
 // parts per block: enough workgroups for two rounds on the 256 CUs, at least 32 stages each (tuning: ksplit forced)
 static int band_ksplit(const ltmi_masks *m, int64_t gx, int n_blocks, int n_stages) {
-    if (m->tune_ksplit > 0) return std::min(m->tune_ksplit, 64);
+    if (m->tune.ksplit > 0) return std::min(m->tune.ksplit, 64);
     const int64_t wgs = gx * n_blocks;
     int k = (int)std::min<int64_t>(16, (512 + wgs - 1) / wgs);
     const int avg = std::max(1, n_stages / std::max(1, n_blocks));

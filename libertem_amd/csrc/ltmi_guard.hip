@@ -154,10 +154,7 @@ static bool out_is_host(NfGuard *g, const void *out) {
 }
 
 static bool guard_enabled() {
-    static const bool on = [] {
-        const char *e = getenv("LTMI_NONFINITE_GUARD");      // 0: the fast kernels' own patterns (timing ablation)
-        return !(e && e[0] == '0');
-    }();
+    const bool on = !switch_is<LTMI_NONFINITE_GUARD>('0');  // 0: the fast kernels' own patterns (timing ablation)
     return on;
 }
 
@@ -321,8 +318,7 @@ int guard_apply(ltmi_masks *m, const MaskCall &call) {
             rc = csr_redo(redo, product, list, ctl);
             if (rc != LTMI_OK) return rc;
         }
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " +nf");
+        append_kernel_note(m, " +nf");
     }
     return guard_deliver(m, call.out, call.ld_out, n_frames, call.accumulate, stream);
 }

@@ -203,7 +203,7 @@ void note_kernel(const char *kernel, int mode, bool quad) {
 // (1-bit words always: 64 bytes of output each), quad rows of 6 / 12 bit in whole chunks per chip row.
 // LTMI_MIB_WORDS in the environment (read per call: tests select the kernel in-process): always k_mib_decode.
 bool mib_wide(int mode, bool quad, int64_t payload, int width, int out_size) {
-    if (getenv("LTMI_MIB_WORDS") != nullptr) return false;
+    if (ltmi::switch_set<ltmi::LTMI_MIB_WORDS>()) return false;
     const int ppc = 16 / out_size;
     return (payload % 16 == 0 || mode == M_R1) && (!quad || mode == M_R1 || ((width / 2) % ppc == 0));
 }

@@ -455,8 +455,9 @@ static ScatImage *build_image(const ScatSet &s, int sz, int *err) {
                     }
                 });
             // (3) chunks: the segments that hold anything, 8 per chunk, composed for level waves
-            static const bool natural = getenv("LTMI_SCATTER_NATURAL") != nullptr;      // (bench: no mixing)
-            static const int unit = std::min(SC_NSEG, getenv("LTMI_SCATTER_SEG") ? std::max(1, atoi(getenv("LTMI_SCATTER_SEG")) / SC_SEG) : 1);
+            const bool natural = switch_set<LTMI_SCATTER_NATURAL>();                     // (bench: no mixing)
+            const char *seg = switch_text<LTMI_SCATTER_SEG>();
+            const int unit = std::min(SC_NSEG, seg ? std::max(1, atoi(seg) / SC_SEG) : 1);
             std::vector<int> segs;                 // groups of `unit` adjacent segments (contiguous bytes of a row)
             for (int g0 = 0; g0 < n_seg; g0 += unit) {
                 bool any = false;
@@ -603,8 +604,7 @@ static int launch_scatter(ltmi_masks *m, ScatImage *b, const MaskCall &call, int
     auto kern = k_scatter<T>;
     int abl = 0;
     if constexpr (std::is_same<T, uint16_t>::value) {
-        const char *e = getenv("LTMI_SCATTER_ABLATE");
-        abl = e ? atoi(e) : 0;
+        abl = switch_int<LTMI_SCATTER_ABLATE>(0);
         if (abl == 1) kern = k_scatter<T, 1>;
         else if (abl == 2) kern = k_scatter<T, 2>;
         else if (abl == 3) kern = k_scatter<T, 3>;

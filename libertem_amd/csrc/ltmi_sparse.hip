@@ -356,8 +356,7 @@ static int launch_sell(ltmi_masks *m, CsrImage *c, const MaskCall &call, const i
     const T *tile = (const T *)call.tile;
     float *out = (float *)call.out;
     const int vec_ok = vector_loads_ok(tile, call.ld_tile, sizeof(T)) ? 1 : 0;
-    const char *abl = getenv("LTMI_SELL_ABLATE");     // 1: loader only, 2: gathers only (bench)
-    const int ablate = abl ? atoi(abl) : 0;
+    const int ablate = switch_int<LTMI_SELL_ABLATE>(0);      // 1: loader only, 2: gathers only (bench)
     dim3 grid((unsigned)((call.n_frames + SP_F - 1) / SP_F), (unsigned)c->n_pass);
     // + one all-zero pixel row (index SP_P) for the padding entries of the image
     const size_t lds = (size_t)(SP_P + 1) * SP_F * sizeof(float);
@@ -579,8 +578,7 @@ int csr_apply(ltmi_masks *m, const MaskCall &call) {
             default: hipLaunchKernelGGL(k_sell_f64_to_int<uint64_t>, grid, dim3(256), 0, stream, src, n_frames, (int)m->n_masks, (uint64_t *)out, ld_out, accumulate); break;
         }
         LTMI_HIP(hipGetLastError());
-        const size_t len = strlen(m->last_kernel);
-        snprintf(m->last_kernel + len, sizeof(m->last_kernel) - len, " exact-int");
+        append_kernel_note(m, " exact-int");
         return LTMI_OK;
     }
     if (c->f64) return csr_apply_f64(m, c, call);
@@ -600,22 +598,20 @@ int csr_apply(ltmi_masks *m, const MaskCall &call) {
     // 1.3 padded MACs per stored entry) runs 3 x faster on the matrix cores (21 ms against 62 ms per 8192 frames
     // of 1024 x 1024, scripts/bench_second_runs.py); C4's rings (4.8) stay here
     const bool bell_better = c->bell && c->bell_ratio > 0. && c->bell_ratio < SCAT_MIN_BELL_RATIO && !c->scat_all;
-    if (c->scat && (c->scat_all || tile_dtype == LTMI_F32) && !bell_better && m->tune_ksplit_ring != 41 &&
-        m->tune_ksplit_ring != 42) {
+    if (c->scat && (c->scat_all || tile_dtype == LTMI_F32) && !bell_better && !m->tune.no_scatter()) {
         bool handled = false;
         const int rc = scat_apply(m, c->scat, c->cplx, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
     // localised stacks: blocked image on the matrix cores (set_tuning 41 forces the SELL kernel)
-    if (c->bell && m->tune_ksplit_ring != 41) {
+    if (c->bell && !m->tune.no_bell()) {
         bool handled = false;
         const int rc = bell_apply(m, c->bell, c->cplx, call, &handled);
         if (rc != LTMI_OK || handled) return rc;
     }
     // a partition stack (it has none of the images above): one multiply-add per labelled pixel, stored entries only
     // like the gather kernel (set_tuning 41 / 42 and a stack that stands for a dense one keep the gather kernel)
-    if (c->labels && labels_takes(tile_dtype) && m->tune_ksplit_ring != 41 && m->tune_ksplit_ring != 42 &&
-        !m->dense_origin)
+    if (c->labels && labels_takes(tile_dtype) && !m->tune.no_labels() && !m->dense_origin)
         return labels_apply(m, c->labels, f32);
     switch (tile_dtype) {
         case LTMI_BOOL:
@@ -813,8 +809,8 @@ static int create_csr(int device, const int64_t *indptr, const int64_t *indices,
     // image of ltmi_bell.hip; the padding factor decides.  LTMI_SPARSE_BELL=0 / 1 forces never /
     // always (tests), LTMI_BELL_MAX_RATIO moves the threshold.
     {
-        const char *force = getenv("LTMI_SPARSE_BELL");
-        const char *thr = getenv("LTMI_BELL_MAX_RATIO");
+        const char *force = switch_text<LTMI_SPARSE_BELL>();
+        const char *thr = switch_text<LTMI_BELL_MAX_RATIO>();
         const double max_ratio = thr ? atof(thr) : 8.0;
         bool build = nnz > 0 && !c->f64 && !gather_only;   // (the blocked image is float32 only)
         if (force && force[0] == '0') build = false;
@@ -837,7 +833,7 @@ static int create_csr(int device, const int64_t *indptr, const int64_t *indices,
     // (ltmi_scatter.hip: exact float32 FMAs on the vector ALUs, every 1- / 2- / 4-byte pixel type).
     // LTMI_SPARSE_SCATTER=0 / 1 forces never / always.
     {
-        const char *force = getenv("LTMI_SPARSE_SCATTER");
+        const char *force = switch_text<LTMI_SPARSE_SCATTER>();
         bool build = nnz > 0 && !c->f64 && n_masks * nc >= 64;
         if (gather_only || (force && force[0] == '0')) build = false;
         else if (force && force[0] == '1') { build = nnz > 0 && !c->f64; c->scat_all = true; }
@@ -853,7 +849,7 @@ static int create_csr(int device, const int64_t *indptr, const int64_t *indices,
     // the gather kernel.  LTMI_SPARSE_LABELS=1 gives it the label image of ltmi_labels.hip instead; unset or 0: never
     // (k_labels is not yet faster than the gather kernel).
     {
-        const char *force = getenv("LTMI_SPARSE_LABELS");
+        const char *force = switch_text<LTMI_SPARSE_LABELS>();
         bool build = result_dtype == LTMI_F32 && !gather_only && !c->bell && !c->scat && force && force[0] == '1';
         if (build) build = ltmi::labels_qualifies(indptr, n_px, n_masks);
         if (build) {

@@ -419,11 +419,7 @@ static int split_kb(int ng) { return 128 / ng; }
 
 // opt-in: LTMI_SPLIT=1 in the environment, or tuning code 36 on the handle
 bool split_selected(bool tuned) {
-    static const bool on = [] {
-        const char *e = getenv("LTMI_SPLIT");
-        return e && e[0] == '1';
-    }();
-    return on || tuned;
+    return switch_is<LTMI_SPLIT>('1') || tuned;
 }
 
 bool split_wanted(int n_cols, int64_t n_px) {
@@ -481,7 +477,7 @@ static int launch_split(ltmi_masks *m, SplitImage *im, const MaskCall &call) {
     }
     const int64_t gx = (call.n_frames + CFG::WG_ROWS - 1) / CFG::WG_ROWS;
     const int64_t gz = im->n_gt;
-    int ksplit = m->tune_ksplit;
+    int ksplit = m->tune.ksplit;
     if (ksplit <= 0) ksplit = choose_ksplit(gx * gz, im->n_slots);
     ksplit = clamp_ksplit(std::max(1, std::min(ksplit, im->n_slots)), im->n_slots);
     if (ksplit > 1) {
@@ -510,10 +506,7 @@ int split_apply(ltmi_masks *m, void *image, const MaskCall &call) {
     SplitImage *im = (SplitImage *)image;
     // 256-frame workgroups once there are enough frames to fill the chip with them (LTMI_SPLIT_TILES
     // = 2 / 4 in the environment forces one shape: benches)
-    static const int forced = [] {
-        const char *e = getenv("LTMI_SPLIT_TILES");
-        return e ? atoi(e) : 0;
-    }();
+    const int forced = switch_int<LTMI_SPLIT_TILES>(0);
     const bool big = forced ? forced == 4 : call.n_frames >= 2048;
 #define LTMI_SPLIT_GO(NG_) return big ? launch_split<NG_, 4>(m, im, call) : launch_split<NG_, 2>(m, im, call);
     if (im->ng == 4) { LTMI_SPLIT_GO(4) }

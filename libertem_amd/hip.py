@@ -5,6 +5,7 @@ There is deliberately NO CPU fallback anywhere in this module: if the shared lib
 missing or a call fails, a `RuntimeError` / `ValueError` is raised.
 """
 import ctypes
+import enum
 import os
 import threading
 
@@ -25,6 +26,24 @@ _DTYPES = {
     np.dtype('int64'): 8, np.dtype('float32'): 9, np.dtype('float64'): 10,
     np.dtype('complex64'): 11, np.dtype('complex128'): 12,
 }
+
+
+class Variant(enum.IntEnum):
+    """enum ltmi_variant (include/ltmi.h): the kernel-variant codes of `MaskHandle.set_tuning(0, code, ksplit)`"""
+    NONE = 0
+    DENSE_DEFAULT = 30
+    DENSE_NO_DMA = 31
+    DENSE_NO_MFMA = 32
+    DENSE_PADDED_GROUPS = 33
+    DENSE_ONE_TILE = 34
+    DENSE_TWO_TILES = 35
+    DENSE_SPLIT_BF16 = 36
+    DENSE_F32_INSTR = 37
+    DENSE_UNFOLDED = 38
+    SPARSE_DEFAULT = 40
+    SPARSE_SELL = 41
+    SPARSE_NO_SCATTER = 42
+
 
 EXPORTS = (
     'ltmi_version', 'ltmi_last_error', 'ltmi_device_count', 'ltmi_device_info',
@@ -496,6 +515,7 @@ class MaskHandle:
         return int(n.value)
 
     def set_tuning(self, mt=0, waves=0, ksplit=0):
+        """(mt, waves, ksplit) of k_dense_mfma, or (0, Variant code, ksplit); plain ints do as well (include/ltmi.h)"""
         check(lib().ltmi_masks_set_tuning(self._ptr, mt, waves, ksplit), 'ltmi_masks_set_tuning')
 
     def last_kernel(self):

@@ -15,6 +15,8 @@ import zlib
 
 import numpy as np
 
+from libertem_amd.hip import Variant as V
+
 OUT_GUARD = 256           # poison bytes in front of and behind a result; keeps the region's base 256-byte aligned
 IN_GUARD = 4096           # fill bytes in front of and behind an input: one 256-pixel float64 mask slot is 2 KiB
 
@@ -207,52 +209,52 @@ CASES = [
     Case('mfma-waves8', 'dense', F32, (1, 8, 1), ('k_dense_mfma<', 'WAVES=8'), (U16,), 16, px(256, below=True),
          rows=False, frames=FRAMES_SMALL),
     # -- k_dense_lds, float32 matrix instruction (integer frames: tuning 37)
-    Case('lds-ng1', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=1,', '!,f16'), (F32,), 16, px(256)),
-    Case('lds-ng2', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=2,', '!,f16'), (F32,), 24, px(128)),
-    Case('lds-ng3', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=3,', '!,f16'), (F32,), 40, px(128)),
-    Case('lds-ng4', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=4,', '!,f16'), (F32,), 64, px(128)),
-    Case('lds-ng1+2valu', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=1+2 VALU'), (F32,), 17, px(128)),
-    Case('lds-ng2+4valu', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=2+4 VALU'), (F32,), 35, px(128)),
-    Case('lds-ng3+2valu', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=3+2 VALU'), (F32,), 50, px(128)),
-    Case('lds-ng0+valu', 'dense', F32, (0, 30, 1), ('k_dense_lds<', 'NG=0+'), (F32,), 3, px(128, two=True)),
-    Case('lds-column-blocks', 'dense', F32, (0, 30, 1), ('column blocks', 'k_dense_lds<'), (F32, U16), 70,
+    Case('lds-ng1', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=1,', '!,f16'), (F32,), 16, px(256)),
+    Case('lds-ng2', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=2,', '!,f16'), (F32,), 24, px(128)),
+    Case('lds-ng3', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=3,', '!,f16'), (F32,), 40, px(128)),
+    Case('lds-ng4', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=4,', '!,f16'), (F32,), 64, px(128)),
+    Case('lds-ng1+2valu', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=1+2 VALU'), (F32,), 17, px(128)),
+    Case('lds-ng2+4valu', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=2+4 VALU'), (F32,), 35, px(128)),
+    Case('lds-ng3+2valu', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=3+2 VALU'), (F32,), 50, px(128)),
+    Case('lds-ng0+valu', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=0+'), (F32,), 3, px(128, two=True)),
+    Case('lds-column-blocks', 'dense', F32, (0, V.DENSE_DEFAULT, 1), ('column blocks', 'k_dense_lds<'), (F32, U16), 70,
          px(128, two=True)),
     # -- exact float16 products (default dispatch) and the float32 instruction on the same frames
     Case('f16-ng1', 'dense', F32, None, ('k_dense_lds<', 'NG=1,', ',f16'), NARROW, 16, px(256)),
     Case('f16-ng2', 'dense', F32, None, ('k_dense_lds<', 'NG=2,', ',f16'), NARROW, 24, px(128)),
     Case('f16-ng3', 'dense', F32, None, ('k_dense_lds<', 'NG=3,', ',f16'), NARROW, 40, px(128)),
     Case('f16-ng4', 'dense', F32, None, ('k_dense_lds<', 'NG=4,', ',f16'), NARROW, 64, px(128)),
-    Case('f32instr-ng1', 'dense', F32, (0, 37, 1), ('k_dense_lds<', 'NG=1,', '!,f16'), NARROW, 16, px(256)),
-    Case('f32instr-ng3', 'dense', F32, (0, 37, 1), ('k_dense_lds<', 'NG=3,', '!,f16'), NARROW, 40, px(128)),
-    Case('f32instr-ng4', 'dense', F32, (0, 37, 1), ('k_dense_lds<', 'NG=4,', '!,f16'), NARROW, 64, px(128)),
+    Case('f32instr-ng1', 'dense', F32, (0, V.DENSE_F32_INSTR, 1), ('k_dense_lds<', 'NG=1,', '!,f16'), NARROW, 16, px(256)),
+    Case('f32instr-ng3', 'dense', F32, (0, V.DENSE_F32_INSTR, 1), ('k_dense_lds<', 'NG=3,', '!,f16'), NARROW, 40, px(128)),
+    Case('f32instr-ng4', 'dense', F32, (0, V.DENSE_F32_INSTR, 1), ('k_dense_lds<', 'NG=4,', '!,f16'), NARROW, 64, px(128)),
     # -- bf16 split (whole mask slots only: no ragged pixel counts on this route)
-    Case('split-ng2', 'dense', F32, (0, 36, 1), ('k_dense_split',), (F32,), 24, (1024, 1152, 2048), rows=False,
+    Case('split-ng2', 'dense', F32, (0, V.DENSE_SPLIT_BF16, 1), ('k_dense_split',), (F32,), 24, (1024, 1152, 2048), rows=False,
          whole_slots=True),
-    Case('split-ng4', 'dense', F32, (0, 36, 1), ('k_dense_split',), (F32,), 50, (1024, 1152, 2048), rows=False,
+    Case('split-ng4', 'dense', F32, (0, V.DENSE_SPLIT_BF16, 1), ('k_dense_split',), (F32,), 50, (1024, 1152, 2048), rows=False,
          whole_slots=True),
     # -- row-mirror fold
-    Case('fold-f32', 'fold', 'complex64', (0, 30, 1), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS, aligned=True),
-    Case('fold-u16', 'fold', 'complex64', (0, 37, 1), ('k_dense_fold16<',), (U16,), 25, sigs=FOLD_SIGS[:1],
+    Case('fold-f32', 'fold', 'complex64', (0, V.DENSE_DEFAULT, 1), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS, aligned=True),
+    Case('fold-u16', 'fold', 'complex64', (0, V.DENSE_F32_INSTR, 1), ('k_dense_fold16<',), (U16,), 25, sigs=FOLD_SIGS[:1],
          aligned=True),
     # -- complex64 stacks
-    Case('c64-8', 'dense', 'complex64', (0, 30, 1), ('k_dense_lds<', 'NG=1,'), (F32, U16), 8, px(256)),
-    Case('c64-25', 'dense', 'complex64', (0, 30, 1), ('k_dense_lds<',), (F32, U16), 25, px(128)),
+    Case('c64-8', 'dense', 'complex64', (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<', 'NG=1,'), (F32, U16), 8, px(256)),
+    Case('c64-25', 'dense', 'complex64', (0, V.DENSE_DEFAULT, 1), ('k_dense_lds<',), (F32, U16), 25, px(128)),
     # -- K splits
-    Case('lds-ng1-ksplit0', 'dense', F32, (0, 30, 0), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256)),
-    Case('lds-ng1-ksplit3', 'dense', F32, (0, 30, 3), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256),
+    Case('lds-ng1-ksplit0', 'dense', F32, (0, V.DENSE_DEFAULT, 0), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256)),
+    Case('lds-ng1-ksplit3', 'dense', F32, (0, V.DENSE_DEFAULT, 3), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256),
          parts=3),
-    Case('lds-ng1-ksplit8', 'dense', F32, (0, 30, 8), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256),
+    Case('lds-ng1-ksplit8', 'dense', F32, (0, V.DENSE_DEFAULT, 8), ('k_dense_lds<', 'NG=1,'), (F32, U16), 16, px_split(256),
          parts=8),
-    Case('lds-ng4-ksplit0', 'dense', F32, (0, 30, 0), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128)),
-    Case('lds-ng4-ksplit3', 'dense', F32, (0, 30, 3), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128),
+    Case('lds-ng4-ksplit0', 'dense', F32, (0, V.DENSE_DEFAULT, 0), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128)),
+    Case('lds-ng4-ksplit3', 'dense', F32, (0, V.DENSE_DEFAULT, 3), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128),
          parts=3),
-    Case('lds-ng4-ksplit8', 'dense', F32, (0, 30, 8), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128),
+    Case('lds-ng4-ksplit8', 'dense', F32, (0, V.DENSE_DEFAULT, 8), ('k_dense_lds<', 'NG=4,'), (F32, U16), 64, px_split(128),
          parts=8),
-    Case('fold-ksplit0', 'fold', 'complex64', (0, 30, 0), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
+    Case('fold-ksplit0', 'fold', 'complex64', (0, V.DENSE_DEFAULT, 0), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
          aligned=True),
-    Case('fold-ksplit3', 'fold', 'complex64', (0, 30, 3), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
+    Case('fold-ksplit3', 'fold', 'complex64', (0, V.DENSE_DEFAULT, 3), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
          aligned=True),
-    Case('fold-ksplit8', 'fold', 'complex64', (0, 30, 8), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
+    Case('fold-ksplit8', 'fold', 'complex64', (0, V.DENSE_DEFAULT, 8), ('k_dense_fold<f',), (F32,), 25, sigs=FOLD_SIGS[:1],
          aligned=True),
     # -- dense, float64 / complex128 / integer results
     Case('lds64', 'dense', 'float64', (0, 0, 1), ('k_dense_lds64',), ('float64', F32, 'int32', U16), 16, px(256)),
@@ -276,9 +278,9 @@ CASES = [
     Case('generic-i64', 'dense', 'int64', None, ('k_dense_generic',), ('int64',), 6, px(256, below=True),
          rows=False),
     # -- CSR handles
-    Case('sell-f32', 'csr', F32, (0, 41, 0), ('k_sell_apply<', '!f64'), (F32, U16, U8), 20, px(256, below=True),
+    Case('sell-f32', 'csr', F32, (0, V.SPARSE_SELL, 0), ('k_sell_apply<', '!f64'), (F32, U16, U8), 20, px(256, below=True),
          frames=FRAMES_SMALL),
-    Case('sell-f64', 'csr', 'float64', (0, 41, 0), ('k_sell_apply<', 'f64'), ('float64', F32, 'int32'), 20,
+    Case('sell-f64', 'csr', 'float64', (0, V.SPARSE_SELL, 0), ('k_sell_apply<', 'f64'), ('float64', F32, 'int32'), 20,
          px(256, below=True), frames=FRAMES_SMALL),
     Case('bell-apply', 'csr', F32, None, ('k_bell_apply',), (F32, U16, U8), 20, px(256, below=True),
          env={'LTMI_SPARSE_BELL': '1', 'LTMI_SPARSE_SCATTER': '0', 'LTMI_BELL_F16': '0'}, frames=FRAMES_SMALL),

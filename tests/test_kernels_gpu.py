@@ -151,7 +151,7 @@ def test_lds_dma_kernel_all_widths(hip, tile_dtype, shape, ksplit):
     else:
         data = (rng.random((n_frames, n_px)) - 0.3).astype(dt)
     masks = (rng.random((n_masks, n_px)) - 0.25).astype(np.float32)
-    res, kern = _apply(hip, data, masks, np.float32, tuning=dict(mt=0, waves=30, ksplit=ksplit))
+    res, kern = _apply(hip, data, masks, np.float32, tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert 'k_dense_lds' in kern, kern          # (1-byte pixels with several groups: 128-byte sub-chunks)
     if ksplit >= 8:
         assert f',{ksplit},' in kern, kern      # (the number of parts the in-turn order is used for)
@@ -162,7 +162,7 @@ def test_lds_dma_kernel_all_widths(hip, tile_dtype, shape, ksplit):
     assert np.all(np.abs(res - ref) <= 1e-5 * scale + 1e-30)
     base = rng.random((n_frames, n_masks)).astype(np.float32)
     res2, _ = _apply(hip, data, masks, np.float32, accumulate_into=base,
-                     tuning=dict(mt=0, waves=30, ksplit=ksplit))
+                     tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert np.all(np.abs(res2 - (ref + base)) <= 1e-5 * (scale + 1))
 
 
@@ -204,11 +204,11 @@ def test_exact_float16_products_for_unsigned_pixels(hip, tile_dtype, shape, kspl
     masks = masks.astype(md)
     ref = _ref64(data, masks)
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
-    tuning = dict(mt=0, waves=30, ksplit=ksplit) if ksplit else None
+    tuning = dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit) if ksplit else None
     res, kern = _apply(hip, data, masks, md, tuning=tuning)
     assert 'k_dense_lds' in kern and ',f16' in kern, kern
     assert np.all(np.abs(res - ref) <= 2e-6 * scale + 1e-30), np.max(np.abs(res - ref) / (scale + 1e-30))
-    res32, kern32 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=37, ksplit=ksplit))
+    res32, kern32 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=hip.Variant.DENSE_F32_INSTR, ksplit=ksplit))
     assert 'k_dense_lds' in kern32 and ',f16' not in kern32, kern32
     assert np.all(np.abs(res32 - res) <= 1e-5 * scale + 1e-30)
     base = (rng.random((n_frames, n_masks)) + (1j * rng.random((n_frames, n_masks))
@@ -500,7 +500,7 @@ def test_long_rows_keep_float32_accuracy(hip, n_px, tile_dtype, n_masks):
     assert err < 4e-6, err
     if n_masks <= 4 and dt.kind != 'f':
         # the VALU-column kernel is still there for them (tuning 37) and agrees
-        res37, kern37 = _apply(hip, data, masks, np.float32, tuning=dict(mt=0, waves=37, ksplit=1))
+        res37, kern37 = _apply(hip, data, masks, np.float32, tuning=dict(mt=0, waves=hip.Variant.DENSE_F32_INSTR, ksplit=1))
         assert 'NG=0+' in kern37, kern37
         assert np.abs(res37 - ref).max() / np.abs(ref).max() < 4e-6
 
@@ -800,7 +800,7 @@ def _apply_csr(hip, data2d, csr_px_by_masks, result_dtype, accumulate_into=None,
     if sig is not None:
         h.set_sig_shape(sig[0], sig[1])
     if tuning is not None or ksplit:
-        h.set_tuning(0, tuning or 40, ksplit)
+        h.set_tuning(0, tuning or hip.Variant.SPARSE_DEFAULT, ksplit)
     t = _dev(np.ascontiguousarray(data2d))
     n_frames, n_px = data2d.shape
     n_masks = csr_px_by_masks.shape[1]
@@ -1253,7 +1253,7 @@ def test_sparse_dispatch_by_padding_factor(hip, monkeypatch):
     ref = f32.astype(np.float64) @ np.asarray(stack.todense()).astype(np.complex128)
     assert np.all(np.abs(res - ref) <= 1e-5 * (np.abs(f32).astype(np.float64) @ np.abs(np.asarray(stack.todense()))) + 1e-30)
     h = hip.MaskHandle.csr(0, sp.csr_matrix(rings.T.astype(np.float32)), np.float32)
-    h.set_tuning(0, 41, 0)                                          # 41: SELL kernel on request
+    h.set_tuning(0, hip.Variant.SPARSE_SELL, 0)                        # the SELL kernel on request
     t, out = _dev(data), _dev(np.zeros((20, 64), dtype=np.float32))
     h.apply(t.data_ptr(), data.dtype, 20, 4096, out.data_ptr(), 64, False)
     torch.cuda.synchronize()
@@ -1480,7 +1480,7 @@ def test_shifted_masks_host_shifts(hip, tile_dtype, sig, n_masks, mask_dtype, ex
             and n_masks * (2 if md.kind == 'c' else 1) > 4:
         assert ',f16' in h.last_kernel(), h.last_kernel()
         assert np.all(np.abs(res - ref) <= 2e-6 * (scale + 1))
-        h.set_tuning(mt=0, waves=37, ksplit=0)
+        h.set_tuning(mt=0, waves=hip.Variant.DENSE_F32_INSTR, ksplit=0)
         out32 = _dev(np.zeros((n, n_masks), dtype=rd))
         h.apply_shifted_host(t.data_ptr(), dt, n, data[0].size, sig[0], sig[1], shifts2,
                              out32.data_ptr(), n_masks, False)
@@ -1523,7 +1523,7 @@ def test_three_groups_plus_valu_columns(hip, tile_dtype, n_masks, mask_dtype, ks
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
     # (integer pixels: tuning 37 keeps the float32 instruction -- by default they take the exact
     # float16 products on a padded group instead of VALU columns, checked at the end)
-    code = 37 if dt.kind in 'iu' else 30
+    code = hip.Variant.DENSE_F32_INSTR if dt.kind in 'iu' else hip.Variant.DENSE_DEFAULT
     res, kern = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=code, ksplit=ksplit))
     n_cols = n_masks * (2 if md.kind == 'c' else 1)
     expect = {17: 'NG=1+2 VALU', 18: 'NG=1+2 VALU', 33: 'NG=2+2 VALU', 34: 'NG=2+2 VALU',
@@ -1536,11 +1536,11 @@ def test_three_groups_plus_valu_columns(hip, tile_dtype, n_masks, mask_dtype, ks
     res2, _ = _apply(hip, data, masks, md, accumulate_into=base,
                      tuning=dict(mt=0, waves=code, ksplit=ksplit))
     assert np.all(np.abs(res2 - (ref + base)) <= 1e-5 * (scale + 1))
-    res4, kern4 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=33, ksplit=ksplit))
+    res4, kern4 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=hip.Variant.DENSE_PADDED_GROUPS, ksplit=ksplit))
     assert ('NG=4' if n_cols > 32 else 'NG=2') in kern4 and 'VALU' not in kern4, kern4
     assert np.all(np.abs(res4 - res) <= 2e-5 * scale + 1e-30)
     if dt.kind in 'iu':
-        res5, kern5 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=30, ksplit=ksplit))
+        res5, kern5 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
         assert ',f16' in kern5 and 'VALU' not in kern5, kern5
         assert np.all(np.abs(res5 - ref) <= 2e-6 * scale + 1e-30)
 
@@ -1572,7 +1572,7 @@ def test_float32_frames_on_bf16_matrix_cores(hip, n_frames, n_px, n_masks, mask_
     ref = _ref64(data, masks)
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
     n_cols = n_masks * (2 if md.kind == 'c' else 1)
-    tuning = dict(mt=0, waves=36, ksplit=ksplit)
+    tuning = dict(mt=0, waves=hip.Variant.DENSE_SPLIT_BF16, ksplit=ksplit)
     res, kern = _apply(hip, data, masks, md, tuning=tuning)
     if n_cols <= 64:
         assert 'k_dense_split' in kern and 'bf16x3' in kern, kern
@@ -1584,7 +1584,7 @@ def test_float32_frames_on_bf16_matrix_cores(hip, n_frames, n_px, n_masks, mask_
     res2, _ = _apply(hip, data, masks, md, accumulate_into=base, tuning=tuning)
     assert np.all(np.abs(res2 - (ref + base)) <= 2e-6 * (scale + 1))
     # the f32-instruction kernel (the default dispatch) agrees
-    res3, kern3 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=30, ksplit=ksplit))
+    res3, kern3 = _apply(hip, data, masks, md, tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert 'k_dense_lds' in kern3, kern3
     assert np.all(np.abs(res3 - res) <= 1e-5 * scale + 1e-30)
     _, kern_default = _apply(hip, data, masks, md)
@@ -2246,9 +2246,9 @@ def test_row_mirror_fold_radial_fourier(hip, sig, n_bins, max_order, n_frames, k
     masks = _radial_stack(sig, n_bins, max_order)
     rng = np.random.default_rng(_seed('fold', sig, n_bins, max_order))
     data = (rng.random((n_frames, sig[0] * sig[1])) - 0.2).astype(np.float32)
-    res, kern = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=30, ksplit=ksplit))
+    res, kern = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert 'k_dense_fold' in kern, kern
-    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=38, ksplit=0))
+    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=hip.Variant.DENSE_UNFOLDED, ksplit=0))
     assert 'k_dense_fold' not in kern_u, kern_u
     ref = _ref64(data, masks)
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
@@ -2257,7 +2257,7 @@ def test_row_mirror_fold_radial_fourier(hip, sig, n_bins, max_order, n_frames, k
         assert np.all(np.abs(part(res) - part(res_u)) <= 2e-5 * scale + 1e-30)
     base = (rng.random((n_frames, masks.shape[0])) + 1j * rng.random((n_frames, masks.shape[0]))).astype(np.complex64)
     res2, kern2 = _fold_apply(hip, data, masks, sig, np.complex64, accumulate_into=base,
-                              tuning=dict(mt=0, waves=30, ksplit=ksplit))
+                              tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert 'k_dense_fold' in kern2
     assert np.all(np.abs(res2 - (ref + base)) <= 1e-5 * (scale + 2))
 
@@ -2341,7 +2341,7 @@ def test_row_mirror_fold_two_waves_per_simd(hip, monkeypatch, sig, n_bins, max_o
     masks = _radial_stack(sig, n_bins, max_order)
     rng = np.random.default_rng(_seed('fold8', sig, n_frames))
     data = (rng.random((n_frames, sig[0] * sig[1])) - 0.2).astype(np.float32)
-    tuning = dict(mt=0, waves=30, ksplit=ksplit) if ksplit else None
+    tuning = dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit) if ksplit else None
     res, kern = _fold_apply(hip, data, masks, sig, np.complex64, tuning=tuning)
     assert 'k_dense_fold8<f' in kern, kern
     ref = _ref64(data, masks)
@@ -2364,7 +2364,7 @@ def test_row_mirror_fold_wide_stack_in_column_blocks(hip):
     data = (rng.random((150, sig[0] * sig[1])) - 0.1).astype(np.float32)
     res, kern = _fold_apply(hip, data, masks, sig, np.complex64)
     assert kern.startswith('3 column blocks') and 'k_dense_fold<f,even=1,odd=1' in kern, kern
-    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=38, ksplit=0))
+    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=hip.Variant.DENSE_UNFOLDED, ksplit=0))
     assert 'k_dense_fold' not in kern_u, kern_u
     ref = _ref64(data, masks)
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
@@ -2390,9 +2390,9 @@ def test_row_mirror_fold_two_byte_pixels(hip, tile_dtype, sig, n_bins, max_order
     data = rng.integers(lo, hi, (n_frames, sig[0] * sig[1]), endpoint=True).astype(dt)
     data[1] = hi
     data[2] = lo
-    res, kern = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=30, ksplit=ksplit))
+    res, kern = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert 'k_dense_fold16' in kern, kern
-    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=38, ksplit=0))
+    res_u, kern_u = _fold_apply(hip, data, masks, sig, np.complex64, tuning=dict(mt=0, waves=hip.Variant.DENSE_UNFOLDED, ksplit=0))
     assert 'k_dense_fold' not in kern_u, kern_u
     ref = _ref64(data, masks)
     scale = np.abs(data.astype(np.float64)) @ np.abs(masks).astype(np.float64).T
@@ -2401,7 +2401,7 @@ def test_row_mirror_fold_two_byte_pixels(hip, tile_dtype, sig, n_bins, max_order
         assert np.all(np.abs(part(res) - part(res_u)) <= 2e-5 * scale + 1e-30)
     base = (rng.random((n_frames, masks.shape[0])) + 1j * rng.random((n_frames, masks.shape[0]))).astype(np.complex64)
     res2, _ = _fold_apply(hip, data, masks, sig, np.complex64, accumulate_into=base,
-                          tuning=dict(mt=0, waves=30, ksplit=ksplit))
+                          tuning=dict(mt=0, waves=hip.Variant.DENSE_DEFAULT, ksplit=ksplit))
     assert np.all(np.abs(res2 - (ref + base)) <= 1e-5 * (scale + 2))
     # every stored weight: one-pixel frames (the mirrored half, the unpaired rows included), rtol 1e-5, atol 0
     n_px = sig[0] * sig[1]
@@ -2460,7 +2460,7 @@ def test_banded_stack_radial_fourier_sparse(hip, monkeypatch, tile_dtype, sig, n
         assert 'banded' not in kern, kern
         return
     assert label in kern and 'banded: %d blocks' % n_bins in kern, kern
-    res_b, kern_b = _apply_csr(hip, data, csr, np.complex64, sig=sig, tuning=42)
+    res_b, kern_b = _apply_csr(hip, data, csr, np.complex64, sig=sig, tuning=hip.Variant.SPARSE_NO_SCATTER)
     assert 'banded' not in kern_b, kern_b
     dense = np.asarray(csr.todense()).astype(np.complex128)
     ref = data.astype(np.float64) @ dense

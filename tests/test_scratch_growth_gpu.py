@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import guarded as G
+from libertem_amd.hip import Variant as V
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -64,10 +65,10 @@ def _grow(run, frames, what):
 # (id, handle, result dtype, tile dtype, n_masks, n_px, tuning, rows, expect, parts: grid.y of a K split)
 PRODUCTS = [
     # K-split partials of the handle (ensure_partials), four parts
-    ('lds-ksplit4', 'dense', 'float32', 'float32', 16, 4096, (0, 30, 4), False, ('k_dense_lds<',), 4),
+    ('lds-ksplit4', 'dense', 'float32', 'float32', 16, 4096, (0, V.DENSE_DEFAULT, 4), False, ('k_dense_lds<',), 4),
     ('mfma-ksplit4', 'dense', 'float32', 'float32', 16, 4096, (1, 4, 4), False, ('k_dense_mfma<',), 4),
     # ... of the bf16 split image
-    ('split-ksplit4', 'dense', 'float32', 'float32', 32, 4096, (0, 36, 4), False, ('k_dense_split<',), 4),
+    ('split-ksplit4', 'dense', 'float32', 'float32', 32, 4096, (0, V.DENSE_SPLIT_BF16, 4), False, ('k_dense_split<',), 4),
     # float64 workspace: the LDS-DMA kernel (frame range and row list) and the direct-load kernel
     ('lds64-ksplit2', 'dense', 'float64', 'float64', 3, 1024, (0, 0, 2), False, ('k_dense_lds64<',), 2),
     ('lds64-ksplit2-rows', 'dense', 'float64', 'float64', 3, 1024, (0, 0, 2), True, ('k_dense_lds64<', ',rows'), 2),

@@ -575,7 +575,7 @@ def test_image_cache(hip, tile_dtype, result_dtype, expect):
     once((16, 32), sets[0], expect, '(16, 32) again')
     once((16, 32), sets[2], [expect[0], '1 group' if expect[0] == L64 else 'shift groups=1'], 'one shift')
     if F16 in expect[1]:
-        h.set_tuning(mt=0, waves=37, ksplit=0)
+        h.set_tuning(mt=0, waves=hip.Variant.DENSE_F32_INSTR, ksplit=0)
         once((16, 32), sets[1], [LDS, 'shifted', '!' + F16], 'tuning 37')
         h.set_tuning(mt=0, waves=0, ksplit=0)
         once((16, 32), sets[0], expect, 'tuning 0 again')
