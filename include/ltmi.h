@@ -628,6 +628,47 @@ int ltmi_correlate_find(ltmi_corr_plan *p, const void *tile, int tile_dtype, int
                         int refine_radius, int32_t *n_found, int32_t *centers, float *refineds, float *peak_values,
                         float *peak_elevations, void *stream);
 
+/* ---- off-axis hologram reconstruction (hipFFT) -----------------------------
+ * With s(i, n) = i for i <= (n-1)/2, else i - n (the signed frequency of index i, fftfreq order), for every frame:
+ *   F = fft2((float)tile[f]) / (sig_h sig_w)
+ *   G[u, v] = F[(sb_y + s(u, out_h)) mod sig_h, (sb_x + s(v, out_w)) mod sig_w] * aperture[u, v]
+ *   wave = the unnormalised inverse DFT of G (= out_h out_w ifft2(G)), times ref_inv elementwise where given
+ * A holography plan owns a batched 2D real-to-complex hipFFT of (sig_h, sig_w), a batched unnormalised
+ * complex-to-complex backward hipFFT of (out_h, out_w), `max_batch` frames per execution, and their workspace: f32
+ * frames, complex64 half spectra and complex64 outputs of one batch.
+ * aperture_host: HOST float32 (out_h, out_w) in the unshifted layout, (0, 0) the sideband centre; stored on the device
+ * as float32(aperture / (sig_h sig_w)), divided in float64.  ref_inv_host: HOST complex64 (out_h, out_w) as float
+ * pairs, 1 / reference_wave, or NULL.
+ * out_h > sig_h, out_w > sig_w, a non-positive shape, a sideband outside [0, sig_h) x [0, sig_w), a batch of more
+ * than 2^31 - 1 pixels: LTMI_E_SHAPE; a null aperture or `out`, max_batch < 1: LTMI_E_INVALID. */
+typedef struct ltmi_holo_plan ltmi_holo_plan;   /* opaque */
+int ltmi_holo_plan_create(int device, int sig_h, int sig_w, int out_h, int out_w, int max_batch, int sb_y, int sb_x,
+                          const float *aperture_host, const float *ref_inv_host, ltmi_holo_plan **out);
+int ltmi_holo_plan_destroy(ltmi_holo_plan *p);
+/* tile: device (n_frames, sig_h*sig_w) of tile_dtype (the dtypes ltmi_correlate_peaks takes), ld_tile elements apart;
+ * out: device complex64 (n_frames, out_h*out_w), rows ld_out elements apart -- nothing between the rows and no row
+ * from n_frames on is written.  Per batch: k_corr_load, R2C, k_holo_crop, C2C backward in place, k_holo_store
+ * (csrc/ltmi_holo.hip).  A frame with a non-finite pixel has an unspecified wave; other frames are unaffected.  No
+ * atomics: the results of a call repeat bit for bit.  Nothing is read back and the stream is not drained.
+ * n_frames < 0, ld_tile < sig_h sig_w, ld_out < out_h out_w: LTMI_E_SHAPE; an unsupported tile dtype: LTMI_E_DTYPE;
+ * a null pointer: LTMI_E_INVALID.  n_frames == 0 launches nothing. */
+int ltmi_holo_reconstruct(ltmi_holo_plan *p, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
+                          void *out, int64_t ld_out, void *stream);
+/* The kernels of the last launching ltmi_holo_reconstruct call of this plan:
+ * "k_corr_load<dtype> + hipfft_r2c + k_holo_crop + hipfft_c2c + k_holo_store batch=N".  The string lives as long as
+ * the plan. */
+const char *ltmi_holo_plan_last_kernel(const ltmi_holo_plan *p);
+/* Step 2 alone, on half spectra the caller supplies: spec is DEVICE complex64, frame f's (h, w/2 + 1) half spectrum
+ * (what a real-to-complex transform of (h, w) stores) at spec + f * ld_spec elements.  Output element (u, v) reads
+ * ky = (sb_y + s(u, out_h)) mod h, kx = (sb_x + s(v, out_w)) mod w: spec[ky, kx] for kx <= w/2, else
+ * conj(spec[(h - ky) mod h, w - kx]); both components are multiplied by aperture_dev[u, v] (DEVICE float32
+ * (out_h, out_w), used as it is) -- one float32 multiply each, so the result is defined bit for bit.  g_out: device
+ * complex64, frame f at g_out + f * ld_g elements.  One launch of k_holo_crop.  Shape errors as for the plan, and
+ * ld_spec < h (w/2 + 1), ld_g < out_h out_w, n_frames < 0: LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID.
+ * n_frames == 0 launches nothing. */
+int ltmi_holo_crop(int device, const void *spec, int64_t n_frames, int h, int w, int64_t ld_spec, int out_h, int out_w,
+                   int sb_y, int sb_x, const float *aperture_dev, void *g_out, int64_t ld_g, void *stream);
+
 /* ---- lattice fit to the matched peaks -------------------------------------------------------------
  * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]
  * (1 where `weights` is NULL), integer lattice indices (i_k, j_k) = indices[k] (precondition |i|, |j| <= 2^20),

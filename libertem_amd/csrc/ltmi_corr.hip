@@ -7,8 +7,7 @@
 // the frame workspace, k_corr_peaks (one wave per (frame, peak)).  The correlation never leaves the plan's workspace.
 // ltmi_correlate_find (section 4.6d) runs the same transforms and then, in place of k_corr_peaks, the search of
 // ltmi_peakfind.hip for the strongest local maxima of every map, rated by k_corr_found on the window code of k_corr_peaks.
-#include "ltmi_common.h"
-#include <hipfft/hipfft.h>
+#include "ltmi_fftshare.h"
 #include <algorithm>
 #include <new>
 
@@ -28,8 +27,6 @@ struct ltmi_corr_plan {
 };
 
 namespace ltmi {
-
-const char *fft_err(hipfftResult r);   // ltmi_fft.hip
 
 // frames (native dtype, ld elements apart) -> contiguous f32.  A thread converts 8 consecutive pixels (one 16-B load
 // for 2-byte pixels, two 16-B stores) where base and rows are 16-B aligned, single pixels otherwise.
@@ -220,7 +217,7 @@ static int run_corr_load(const void *tile, int64_t ld, int64_t n, int64_t n_px, 
     return LTMI_OK;
 }
 
-static bool corr_takes(int tile_dtype) {
+bool corr_takes(int tile_dtype) {
     switch (tile_dtype) {
         case LTMI_BOOL: case LTMI_U8: case LTMI_I8: case LTMI_U16: case LTMI_I16: case LTMI_U32: case LTMI_I32:
         case LTMI_F32: case LTMI_F64: return true;
@@ -228,8 +225,7 @@ static bool corr_takes(int tile_dtype) {
     }
 }
 
-static int corr_load(const void *src, int tile_dtype, int64_t ld, int64_t n, int64_t n_px, float *out,
-                     hipStream_t stream) {
+int corr_load(const void *src, int tile_dtype, int64_t ld, int64_t n, int64_t n_px, float *out, hipStream_t stream) {
     switch (tile_dtype) {
         case LTMI_BOOL:
         case LTMI_U8: return run_corr_load<uint8_t>(src, ld, n, n_px, out, stream);
@@ -240,7 +236,7 @@ static int corr_load(const void *src, int tile_dtype, int64_t ld, int64_t n, int
         case LTMI_I32: return run_corr_load<int32_t>(src, ld, n, n_px, out, stream);
         case LTMI_F32: return run_corr_load<float>(src, ld, n, n_px, out, stream);
         case LTMI_F64: return run_corr_load<double>(src, ld, n, n_px, out, stream);
-        default: LTMI_FAIL(LTMI_E_DTYPE, "ltmi_correlate_peaks: unsupported tile dtype %s", dtype_name(tile_dtype));
+        default: LTMI_FAIL(LTMI_E_DTYPE, "k_corr_load: unsupported tile dtype %s", dtype_name(tile_dtype));
     }
 }
 

@@ -6,8 +6,7 @@
 // ONE batched 2D real-to-complex hipFFT per batch of frames, and a fused |F| * mask reduction that
 // reads the half spectrum once and writes one float per frame.  The spectrum never leaves the
 // plan's workspace.
-#include "ltmi_common.h"
-#include <hipfft/hipfft.h>
+#include "ltmi_fftshare.h"
 #include <algorithm>
 #include <new>
 
@@ -30,7 +29,7 @@ struct ltmi_fft_plan {
 
 namespace ltmi {
 
-const char *fft_err(hipfftResult r) {   // (shared with ltmi_corr.hip)
+const char *fft_err(hipfftResult r) {   // (ltmi_fftshare.h)
     switch (r) {
         case HIPFFT_SUCCESS: return "success";
         case HIPFFT_INVALID_PLAN: return "invalid plan";

@@ -58,6 +58,8 @@ EXPORTS = (
     'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
     'ltmi_lattice_fit', 'ltmi_lattice_last_kernel',
     'ltmi_find_peaks_maps', 'ltmi_find_peaks_last_kernel', 'ltmi_correlate_find',
+    'ltmi_holo_plan_create', 'ltmi_holo_plan_destroy', 'ltmi_holo_reconstruct', 'ltmi_holo_plan_last_kernel',
+    'ltmi_holo_crop',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -348,6 +350,12 @@ def lib():
         L.ltmi_find_peaks_last_kernel.restype = c.c_char_p
         L.ltmi_correlate_find.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, c.c_float, c.c_float, i32,
                                           vp, vp, vp, vp, vp, vp]
+        L.ltmi_holo_plan_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, c.POINTER(vp)]
+        L.ltmi_holo_plan_destroy.argtypes = [vp]
+        L.ltmi_holo_reconstruct.argtypes = [vp, vp, i32, i64, i64, vp, i64, vp]
+        L.ltmi_holo_plan_last_kernel.argtypes = [vp]
+        L.ltmi_holo_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_holo_crop.argtypes = [i32, vp, i64, i32, i32, i64, i32, i32, i32, i32, vp, vp, i64, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -1054,6 +1062,69 @@ def find_peaks_last_kernel():
     """'k_pf_cells + k_pf_verify + k_pf_select + k_corr_found' after the first launching `find_peaks_maps` call
     on this thread, '' before"""
     return lib().ltmi_find_peaks_last_kernel().decode()
+
+
+class HoloPlan:
+    """Owns one `ltmi_holo_plan*`: a batched 2D R2C hipFFT of (sig_h, sig_w), a batched backward C2C hipFFT of
+    (out_h, out_w) and their workspace, the sideband position (sb_y, sb_x) in the unshifted fft2 layout, the real
+    aperture (host float32 (out_h, out_w), unshifted layout, (0, 0) the sideband centre) and, optionally, a complex
+    reference wave of the same shape, inverted here in complex128 and stored as complex64."""
+
+    def __init__(self, device, sig_h, sig_w, out_h, out_w, max_batch, sb_y, sb_x, aperture, reference_wave=None):
+        out_shape = (int(out_h), int(out_w))
+        a = np.ascontiguousarray(aperture, dtype=np.float32)
+        if a.shape != out_shape:
+            raise ValueError(f"aperture of shape {a.shape} for an output of {out_shape}")
+        ref_inv = None
+        if reference_wave is not None:
+            ref = np.asarray(reference_wave)
+            if ref.shape != out_shape:
+                raise ValueError(f"reference_wave of shape {ref.shape} for an output of {out_shape}")
+            with np.errstate(all='ignore'):
+                ref_inv = np.ascontiguousarray((1.0 / ref.astype(np.complex128)).astype(np.complex64))
+        out = ctypes.c_void_p()
+        check(lib().ltmi_holo_plan_create(
+            int(device), int(sig_h), int(sig_w), out_shape[0], out_shape[1], int(max_batch), int(sb_y), int(sb_x),
+            a.ctypes.data_as(ctypes.c_void_p),
+            None if ref_inv is None else ref_inv.ctypes.data_as(ctypes.c_void_p), ctypes.byref(out)),
+            'ltmi_holo_plan_create')
+        self._ptr = out
+        self.device, self.sig, self.out_shape = int(device), (int(sig_h), int(sig_w)), out_shape
+        self.max_batch, self.sb_position = int(max_batch), (int(sb_y), int(sb_x))
+
+    def reconstruct(self, tile_ptr, tile_dtype, n_frames, ld_tile, out_ptr, ld_out, stream=None):
+        """tile: device (n_frames, sig_h * sig_w) of tile_dtype, ld_tile elements apart; out: device complex64
+        (n_frames, out_h * out_w), rows ld_out elements apart (include/ltmi.h)."""
+        check(lib().ltmi_holo_reconstruct(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), out_ptr, int(ld_out),
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_holo_reconstruct')
+
+    def last_kernel(self):
+        """'k_corr_load<...> + hipfft_r2c + k_holo_crop + hipfft_c2c + k_holo_store batch=N' after the first launching
+        `reconstruct` call, '' before"""
+        return lib().ltmi_holo_plan_last_kernel(self._ptr).decode()
+
+    def close(self):
+        if self._ptr is not None and self._ptr.value:
+            lib().ltmi_holo_plan_destroy(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def holo_crop(device, spec_ptr, n_frames, h, w, ld_spec, out_h, out_w, sb_y, sb_x, aperture_ptr, g_ptr, ld_g,
+              stream=None):
+    """The sideband gather of `HoloPlan.reconstruct` on complex64 half spectra the caller supplies: frame f's
+    (h, w // 2 + 1) half spectrum at spec + f * ld_spec elements, the float32 aperture (out_h, out_w) on the device,
+    used as it is; frame f's (out_h, out_w) result at g + f * ld_g elements (include/ltmi.h)."""
+    check(lib().ltmi_holo_crop(
+        int(device), spec_ptr, int(n_frames), int(h), int(w), int(ld_spec), int(out_h), int(out_w), int(sb_y),
+        int(sb_x), aperture_ptr, g_ptr, int(ld_g), stream if isinstance(stream, int) else _stream_ptr(stream)),
+        'ltmi_holo_crop')
 
 
 def lattice_fit(device, refineds_ptr, weights_ptr, peak_values_ptr, n_frames, n_peaks, indices_ptr, start, tolerance,
