@@ -32,19 +32,22 @@ namespace ltmi {
 // for 2-byte pixels, two 16-B stores) where base and rows are 16-B aligned, single pixels otherwise.
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_corr_load(const T *__restrict__ tile, int64_t ld, int64_t n_px, float *__restrict__ out, int vec_ok) {
-    const int64_t f = blockIdx.y;
-    const T *src = tile + f * ld;
-    float *dst = out + f * n_px;
+k_corr_load(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n_px, float *__restrict__ out,
+            int vec_ok) {
     const int64_t n8 = vec_ok ? n_px / 8 : 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-        typedef T __attribute__((ext_vector_type(8))) vec_t;
-        const vec_t x = __builtin_nontemporal_load((const vec_t *)(src + i * 8));
-        *(float4 *)(dst + i * 8) = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
-        *(float4 *)(dst + i * 8 + 4) = make_float4((float)x[4], (float)x[5], (float)x[6], (float)x[7]);
+    // (the grid's y extent is capped at CORR_MAX_GRID_Y: a block walks every gridDim.y-th frame)
+    for (int64_t f = blockIdx.y; f < n_frames; f += gridDim.y) {
+        const T *src = tile + f * ld;
+        float *dst = out + f * n_px;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+            typedef T __attribute__((ext_vector_type(8))) vec_t;
+            const vec_t x = __builtin_nontemporal_load((const vec_t *)(src + i * 8));
+            *(float4 *)(dst + i * 8) = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
+            *(float4 *)(dst + i * 8 + 4) = make_float4((float)x[4], (float)x[5], (float)x[6], (float)x[7]);
+        }
+        for (int64_t p = n8 * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)gridDim.x * 256)
+            dst[p] = (float)src[p];
     }
-    for (int64_t p = n8 * 8 + (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)gridDim.x * 256)
-        dst[p] = (float)src[p];
 }
 
 // tspec[i] = conj(spec[i]) * scale: the template's spectrum from the plan's own forward transform
@@ -66,18 +69,20 @@ k_corr_mul(hipfftComplex *__restrict__ spec, const hipfftComplex *__restrict__ t
     if (i >= n_spec) return;
     typedef float __attribute__((ext_vector_type(2 * V))) vec_t;
     const vec_t t = *(const vec_t *)(tspec + i);
-    const int64_t f0 = (int64_t)blockIdx.y * fpb;
-    const int64_t f1 = min(n_frames, f0 + fpb);
-    for (int64_t f = f0; f < f1; ++f) {
-        vec_t *p = (vec_t *)(spec + f * n_spec + i);
-        const vec_t s = *p;
-        vec_t o;
+    // (the grid's y extent is capped at CORR_MAX_GRID_Y: a block walks every gridDim.y-th group of fpb frames)
+    for (int64_t f0 = (int64_t)blockIdx.y * fpb; f0 < n_frames; f0 += (int64_t)gridDim.y * fpb) {
+        const int64_t f1 = min(n_frames, f0 + fpb);
+        for (int64_t f = f0; f < f1; ++f) {
+            vec_t *p = (vec_t *)(spec + f * n_spec + i);
+            const vec_t s = *p;
+            vec_t o;
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            o[2 * j] = s[2 * j] * t[2 * j] - s[2 * j + 1] * t[2 * j + 1];
-            o[2 * j + 1] = s[2 * j] * t[2 * j + 1] + s[2 * j + 1] * t[2 * j];
+            for (int j = 0; j < V; ++j) {
+                o[2 * j] = s[2 * j] * t[2 * j] - s[2 * j + 1] * t[2 * j + 1];
+                o[2 * j + 1] = s[2 * j] * t[2 * j + 1] + s[2 * j + 1] * t[2 * j];
+            }
+            *p = o;
         }
-        *p = o;
     }
 }
 
@@ -206,13 +211,17 @@ k_corr_found(const float *__restrict__ maps, int64_t ld_map, int h, int w, int64
     corr_window(maps + f * ld_map, h, w, py, px, r, q, lane, o, centers, refineds, peak_values, peak_elevations);
 }
 
+// gridDim.y of k_corr_load and k_corr_mul: the frames of a batch (max_batch of the plan, bounded only by 2^31 - 1
+// pixels) beyond it are walked by the kernels' frame loops, as in ltmi_fft.hip
+constexpr int64_t CORR_MAX_GRID_Y = 65535;
+
 template <typename T>
 static int run_corr_load(const void *tile, int64_t ld, int64_t n, int64_t n_px, float *out, hipStream_t stream) {
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_px / 8 + 255) / 256, 32));
     const int vec_ok = (sizeof(T) <= 4) && ((uintptr_t)tile % 16 == 0) && ((ld * (int64_t)sizeof(T)) % 16 == 0) &&
                        (n_px % 8 == 0);
-    hipLaunchKernelGGL((k_corr_load<T>), dim3(gx, (unsigned)n), dim3(256), 0, stream, (const T *)tile, ld, n_px, out,
-                       vec_ok);
+    hipLaunchKernelGGL((k_corr_load<T>), dim3(gx, (unsigned)std::min(n, CORR_MAX_GRID_Y)), dim3(256), 0, stream,
+                       (const T *)tile, ld, n, n_px, out, vec_ok);
     LTMI_HIP(hipGetLastError());
     return LTMI_OK;
 }
@@ -243,12 +252,12 @@ int corr_load(const void *src, int tile_dtype, int64_t ld, int64_t n, int64_t n_
 static void corr_mul(ltmi_corr_plan *p, int64_t n, hipStream_t stream) {
     const int n_spec = p->h * p->wc;
     const int fpb = 8;
-    const dim3 grid_y((unsigned)((n + fpb - 1) / fpb));
+    const unsigned gy = (unsigned)std::min((n + fpb - 1) / fpb, CORR_MAX_GRID_Y);
     if (n_spec % 2 == 0)
-        hipLaunchKernelGGL((k_corr_mul<2>), dim3((unsigned)((n_spec / 2 + 255) / 256), grid_y.x), dim3(256), 0, stream,
+        hipLaunchKernelGGL((k_corr_mul<2>), dim3((unsigned)((n_spec / 2 + 255) / 256), gy), dim3(256), 0, stream,
                            (hipfftComplex *)p->spec, (const hipfftComplex *)p->tspec, n_spec, n, fpb);
     else
-        hipLaunchKernelGGL((k_corr_mul<1>), dim3((unsigned)((n_spec + 255) / 256), grid_y.x), dim3(256), 0, stream,
+        hipLaunchKernelGGL((k_corr_mul<1>), dim3((unsigned)((n_spec + 255) / 256), gy), dim3(256), 0, stream,
                            (hipfftComplex *)p->spec, (const hipfftComplex *)p->tspec, n_spec, n, fpb);
 }
 

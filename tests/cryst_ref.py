@@ -12,6 +12,14 @@ import numpy as np
 F32_TOL = 1e-5             # the project's tolerance for float32 results against float64 (north star)
 SAME_FRAMES_RTOL = 2e-6    # ... between two conversions of the same frames
 
+# pixel values at the ends of a type's range and around 2^24, where float32 stops holding every integer: planted by
+# the tests of the conversion kernels (k_fft_prepare here, k_corr_load in tests/correlation_ref.py)
+EXTREMES = {
+    'uint32': [2**32 - 1, 2**32 - 2, 2**32 - 129, 2**31, 2**31 + 1, 2**24 + 1, 2**24 + 3, 0],
+    'int32': [2**31 - 1, 2**31 - 65, -2**31, -2**31 + 1, 2**24 + 1, -2**24 - 1, 2**30 + 1, -1],
+    'float64': [16777217.0, 123456789.123, -98765432.1, 2.0**24 + 3, 1.0 + 2.0**-30, -16777219.0, 0.1, 3e7 + 0.5],
+}
+
 
 def _dev(arr):
     import torch

@@ -22,6 +22,8 @@ inverse to complex64 and one complex float32 multiply, each below 1.2 eps32, dou
 """
 import numpy as np
 
+from correlation_ref import EXTREMES, POOL
+
 EPS32 = float(np.finfo(np.float32).eps)
 C_BOUND = 8.0
 
@@ -97,6 +99,33 @@ def noise_frames(sig, n, dtype, seed=0):
         info = np.iinfo(dt)
         return rng.integers(max(info.min, -2000), min(info.max, 4000), (n,) + tuple(sig), endpoint=True).astype(dt)
     return ((rng.random((n,) + tuple(sig)) - 0.3) * 50).astype(dt)
+
+
+def typed_frames(sig, n, dtype, seed=0):
+    """noise_frames, and for uint32 (n >= 3) the values of EXTREMES in frame 2: the ends of the range, 2^31 and its
+    neighbours, 2^24 + 1"""
+    frames = noise_frames(sig, n, dtype, seed)
+    if np.dtype(dtype).name == 'uint32' and n >= 3:
+        v = np.array(EXTREMES['uint32']).astype(frames.dtype)
+        at = np.linspace(0, sig[0] * sig[1] - 1, len(v)).astype(int)
+        frames[2].reshape(-1)[at] = v
+    return frames
+
+
+# tiles of many frames drawn from a pool (correlation_ref.pool_index): 8 x 8 -> 4 x 4, the sideband in the mirrored
+# half: columns 6, 7 and 5 are mirrored ones, 4 is the stored Nyquist column
+POOL_CASE = ((8, 8), (4, 4), (1, 6))
+
+
+def pool_frames():
+    return noise_frames(POOL_CASE[0], POOL, 'uint8', seed=9)
+
+
+def pool_spectra():
+    """POOL random complex64 half spectra (8, 5)"""
+    rng = np.random.default_rng([9, 5])
+    shape = (POOL, POOL_CASE[0][0], POOL_CASE[0][1] // 2 + 1)
+    return (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(np.complex64)
 
 
 def carrier_params(sig, k):

@@ -199,6 +199,18 @@ def special_maps(sig, d):
     return m
 
 
+POOL_MAPS = (((8, 8), 41), ((64, 64), 42))     # (sig, seed) of the two tiles of many maps
+
+
+def pool_maps(sig, seed):
+    """cr.POOL quantised float32 maps for tiles of many maps (cr.pool_index); member 7 is constant, member 23 holds a
+    NaN (it keeps nothing)"""
+    m = quantised_maps(sig, cr.POOL, seed)
+    m[7] = 1.5
+    m[23, sig[0] // 3, sig[1] // 3] = np.nan
+    return m
+
+
 def comb_map(n=256, step=3):
     """(1, n, n): one pixel in every step x step block carries a value of its own, the rest is 0: with d = 1 every
     one of them is a peak -- (n // step)^2 of them, more than the selection ranks in one go"""
@@ -285,6 +297,13 @@ def corrected_scan():
     dark = rng.uniform(0., 500., SCAN_SIG)
     gain = rng.uniform(0.95, 1.05, SCAN_SIG)
     return ((frames.astype(np.float64) - dark) * gain).astype(np.float32), dark, gain
+
+
+def pool_case():
+    """the pool of tests/correlation_ref.py searched with d = 1 for up to 3 peaks: -> frames (cr.POOL, 8, 8) uint8,
+    template, parameters.  threshold_abs as threshold_for has it, between a flat frame and the weaker block."""
+    frames, tmpl = cr.pool_frames(), cr.pool_template()
+    return frames, tmpl, params(num_peaks=3, min_distance=1, threshold_abs=threshold_for(frames, tmpl))
 
 
 def undecided_frame():

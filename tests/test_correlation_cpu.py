@@ -177,3 +177,27 @@ def test_kernel_inputs_hold_no_near_tie(case):
     ref = cr.reference(frames, template, peaks, r, q)
     bound = cr.value_bound(frames, template)[:, None]
     assert np.all(ref['gap'] > 2 * bound), float((ref['gap'] / (2 * bound)).min())
+
+
+def test_pool_is_decided_by_the_reference_alone():
+    # the many-frame kernel tests leave out no (frame, peak) pair: every window of every pool member has a top-two
+    # gap above twice the bound, and the members differ, so that a frame taken from another slot shows
+    pool, template = cr.pool_frames(), cr.pool_template()
+    assert pool.shape == (cr.POOL,) + cr.POOL_SIG and pool.dtype == np.uint8
+    assert len({m.tobytes() for m in pool}) == cr.POOL
+    ref = cr.reference(pool, template, cr.POOL_PEAKS, cr.POOL_R, cr.POOL_Q)
+    bound = cr.value_bound(pool, template)[:, None]
+    assert np.all(ref['gap'] > 2 * bound), float((ref['gap'] / (2 * bound)).min())
+    values = ref['peak_values']
+    assert len({v.tobytes() for v in values}) == cr.POOL      # (no two members give the same results)
+
+
+@pytest.mark.parametrize('n,extra', [(70000, ()), (524300, (524279, 524280, 524281)), (16400, (16383, 16384))])
+def test_pool_index_marks_the_frames_at_the_limits(n, extra):
+    idx = cr.pool_index(n, extra)
+    assert idx.shape == (n,) and idx.min() == 0 and idx.max() == cr.POOL - 1
+    assert np.array_equal(idx, cr.pool_index(n, extra))
+    for f in {0, cr.GRID_ROWS - 1, cr.GRID_ROWS, cr.GRID_ROWS + 1, n - 1, *extra}:
+        if f < n:
+            assert all(idx[f] != idx[g] for g in (f - 1, f + 1) if 0 <= g < n), f
+    assert np.all(np.bincount(idx, minlength=cr.POOL) > 0)

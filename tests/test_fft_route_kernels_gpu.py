@@ -14,7 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
-from cryst_ref import F32_TOL, SAME_FRAMES_RTOL, _cryst_reference, _cryst_run, cryst_reference_many
+from cryst_ref import EXTREMES, F32_TOL, SAME_FRAMES_RTOL, _cryst_reference, _cryst_run, cryst_reference_many
 from oracle import corrections as oc
 
 torch = pytest.importorskip("torch")
@@ -149,11 +149,6 @@ def test_single_pixel_frames_every_pixel_of_the_conversion(hip, plans, sig, dtyp
 
 # --- 2b: all pixel types, both prepare branches ----------------------------------------------------------------------
 ALL_DTYPES = ['bool', 'uint8', 'int8', 'uint16', 'int16', 'uint32', 'int32', 'float32', 'float64']
-EXTREMES = {
-    'uint32': [2**32 - 1, 2**32 - 2, 2**32 - 129, 2**31, 2**31 + 1, 2**24 + 1, 2**24 + 3, 0],
-    'int32': [2**31 - 1, 2**31 - 65, -2**31, -2**31 + 1, 2**24 + 1, -2**24 - 1, 2**30 + 1, -1],
-    'float64': [16777217.0, 123456789.123, -98765432.1, 2.0**24 + 3, 1.0 + 2.0**-30, -16777219.0, 0.1, 3e7 + 0.5],
-}
 
 
 def _typed_frames(dtype, corrected):

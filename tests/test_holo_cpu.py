@@ -301,3 +301,20 @@ def test_compat_names():
     finally:
         if not was_active:
             compat.uninstall()
+
+
+def test_pools_of_the_many_frame_tests():
+    # distinct members, and a sideband whose gather reads mirrored columns and the stored Nyquist column
+    from correlation_ref import POOL
+    (h, w), (oh, ow), (sy, sx) = hr.POOL_CASE
+    frames, spec = hr.pool_frames(), hr.pool_spectra()
+    assert frames.shape == (POOL, h, w) and frames.dtype == np.uint8
+    assert spec.shape == (POOL, h, w // 2 + 1) and spec.dtype == np.complex64
+    assert len({m.tobytes() for m in frames}) == POOL and len({m.tobytes() for m in spec}) == POOL
+    kx = sorted((sx + int(s)) % w for s in hr.signed(ow))
+    assert kx == [4, 5, 6, 7]
+    g = hr.gather(spec, (h, w), (oh, ow), (sy, sx), hr.aperture_for(hr.POOL_CASE))
+    assert len({m.tobytes() for m in g}) == POOL
+    # EXTREMES reach the uint32 frames of the kernel tests
+    typed = hr.typed_frames((16, 16), 5, 'uint32')
+    assert typed[2].max() == 2 ** 32 - 1 and (typed[2] == 2 ** 31).sum() == 1 and (typed[2] == 2 ** 24 + 1).sum() == 1

@@ -16,9 +16,10 @@ component leave no rounding freedom.  Frame -> output, sideband, and what the ro
 with 1 and 5 frames and padded ld_spec / ld_g, NaN around the spectra and poison around the results.
 
 The whole route on the same shapes against the float64 restatement, within the bound of tests/holo_ref.py (C = 8, no
-case exempt): uint8, uint16, int16, float32 and float64 tiles; 1 frame; 5 frames in three batches with a partial last
-one; a batch larger than the tile; padded ld_tile and ld_out; with and without a reference wave; guard bytes; bitwise
-repeats; a NaN pixel; no frames; every error code; the `last_kernel` string.
+case exempt): uint8, int8, uint16, int16, uint32 (with the ends of its range), float32 and float64 tiles; 1 frame;
+5 frames in three batches with a partial last one; a batch larger than the tile; padded ld_tile and ld_out; with and
+without a reference wave; guard bytes; bitwise repeats; a NaN pixel; no frames; every error code; the `last_kernel`
+string.
 """
 import ctypes
 
@@ -43,10 +44,10 @@ def random_spectra(case, n):
 class Crop:
     """guarded half spectra, a guarded result and the aperture on the device"""
 
-    def __init__(self, case, n, pad_spec=0, pad_g=0):
+    def __init__(self, case, n, pad_spec=0, pad_g=0, spec_host=None):
         (h, w), (oh, ow), _ = self.case = case
         self.n = n
-        self.spec_host = random_spectra(case, n)
+        self.spec_host = random_spectra(case, n) if spec_host is None else spec_host
         n_spec = h * (w // 2 + 1)
         self.spec = guarded.Region(n, n_spec, n_spec + pad_spec, np.complex64, init=self.spec_host.reshape((n, n_spec)),
                                    fill='nan')
@@ -140,6 +141,8 @@ VARIANTS = [
     ('float64', 5, 2, 5, 0, False),
     ('float32', 1, 4, 0, 0, True),
     ('uint16', 5, 5, 0, 0, False),         # one full batch, contiguous rows: the vector loads of k_corr_load
+    ('int8', 5, 2, 3, 0, False),           # signed bytes, the whole range
+    ('uint32', 5, 2, 0, 2, True),          # 2^32 - 1, 2^31, 2^31 + 1 and 2^24 + 1 in frame 2 (holo_ref.typed_frames)
 ]
 
 
@@ -147,7 +150,7 @@ VARIANTS = [
 @pytest.mark.parametrize('case', hr.CASES, ids=hr.case_id)
 def test_reconstruct_vs_definition(case, variant):
     dtype, n, max_batch, pad_tile, pad_out, with_reference = variant
-    frames = hr.noise_frames(case[0], n, dtype)
+    frames = hr.typed_frames(case[0], n, dtype)
     call = Call(case, frames, max_batch, pad_tile, pad_out, with_reference)
     got = call.run()
     call.compare(got, what=f"{hr.case_id(case)} {dtype}")

@@ -266,3 +266,18 @@ def test_scans_are_decided_and_the_noisy_frame_is_not():
     assert int((~pr.all_decided(pr.corrected_scan()[0], tmpl, p)).sum()) == 0
     noisy, tmpl, p = pr.undecided_frame()
     assert not pr.all_decided(noisy, tmpl, p)[0]              # (held to properties only on the GPU)
+
+
+def test_pool_is_decided():
+    # the many-frame tests: every member of the 8 x 8 pool keeps the same peaks under any error within the bound, some
+    # members keep one peak and some two; the map pools hold distinct members, a constant one and one with a NaN
+    frames, tmpl, p = pr.pool_case()
+    assert int((~pr.all_decided(frames, tmpl, p)).sum()) == 0
+    maps = np.stack([cr.correlation(f, tmpl) for f in frames])
+    n_found = pr.reference(maps, **p)['n_found']
+    assert set(n_found) == {1, 2}
+    for sig, seed in pr.POOL_MAPS:
+        pool = pr.pool_maps(sig, seed)
+        assert pool.shape == (cr.POOL,) + sig and pool.dtype == np.float32
+        assert len({m.tobytes() for m in pool}) == cr.POOL
+        assert np.all(pool[7] == 1.5) and np.isnan(pool[23]).sum() == 1 and np.isfinite(np.delete(pool, 23, 0)).all()
