@@ -669,6 +669,66 @@ const char *ltmi_holo_plan_last_kernel(const ltmi_holo_plan *p);
 int ltmi_holo_crop(int device, const void *spec, int64_t n_frames, int h, int w, int64_t ld_spec, int out_h, int out_w,
                    int sb_y, int sb_x, const float *aperture_dev, void *g_out, int64_t ld_g, void *stream);
 
+/* ---- single-sideband ptychography (hipFFT) ---------------------------------
+ * For a scan of (nav_y, nav_x) positions of real frames, P bright-field pixels K listed by their row-major frame
+ * index idx[K] (pixel (y, x) = (idx / sig_w, idx % sig_w)), s(i, n) the signed frequency of index i as above, and the
+ * geometry geom[LTMI_SSB_GEOM] = { lamb, dy, dx, semiconv, semiconv_pix, cy, cx, t00, t01, t10, t11 } (HOST doubles):
+ *   G[K, iy, ix] = sum over the scan positions (ry, rx) of bf[ry nav_x + rx, K] exp(-2 pi i (s(iy) ry / nav_y +
+ *                  s(ix) rx / nav_x))                          (the unnormalised DFT over the scan axes)
+ *   for Q = (iy, ix) != (0, 0):
+ *     qy = s(iy) / (nav_y dy), qx = s(ix) / (nav_x dx)
+ *     d  = ((t00 qy + t01 qx) lamb semiconv_pix / semiconv, (t10 qy + t11 qx) lamb semiconv_pix / semiconv)
+ *     in+(K) = (y - (cy + d_y))^2 + (x - (cx + d_x))^2 < semiconv_pix^2,   in-(K) the same with (cy - d_y, cx - d_x)
+ *     pos = in+ and not in-, neg = in- and not in+, over the LISTED pixels (the caller lists the pixels of the disk
+ *     (y - cy)^2 + (x - cx)^2 < semiconv_pix^2; the library does not test that)
+ *     fourier[Q] = (sum_pos G[K, Q] / |pos| - sum_neg G[K, Q] / |neg|) / 2 if |pos| >= cutoff and |neg| >= cutoff,
+ *                  else 0
+ *   fourier[0, 0] = sum over all listed K of G[K, 0, 0] / P
+ * The predicates are evaluated on the device in float64, every product, quotient and sum rounded on its own and in
+ * the order written (products and quotients left to right): they agree with a NumPy float64 evaluation bit for bit.
+ * The sums over K accumulate in float64 in a fixed order (thread, wave shuffle tree, waves in order, batches in
+ * order), the quotients are float64, the result is cast to complex64 once.  No atomics: the results of a call repeat
+ * bit for bit.  Every Q is computed from its own d; nothing is filled in by symmetry. */
+#define LTMI_SSB_GEOM 11
+/* The bright-field pixels of every frame: out[f, k] = (float)tile[f, idx[k]].  tile: device (n_frames, n_px) of
+ * tile_dtype (the dtypes ltmi_correlate_peaks takes), ld_tile elements apart; idx_dev: DEVICE int32 (n_idx), frame
+ * indices in any order -- an index outside [0, n_px) reads nothing and gives 0; out: device float32 (n_frames, n_idx),
+ * rows ld_out elements apart -- nothing between the rows and no row from n_frames on is written.  One launch of
+ * k_ssb_gather<dtype> (csrc/ltmi_ssb.hip), which converts in registers and walks the frames beyond 65535 grid rows in
+ * a loop.  n_frames == 0 or n_idx == 0 launches nothing.  n_frames < 0, n_idx < 0, n_px < 1, ld_tile < n_px,
+ * ld_out < n_idx: LTMI_E_SHAPE; an unsupported tile dtype: LTMI_E_DTYPE; a null pointer: LTMI_E_INVALID. */
+int ltmi_ssb_gather(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, int64_t n_px,
+                    const int32_t *idx_dev, int n_idx, float *out, int64_t ld_out, void *stream);
+/* A plan owns the list (idx_host: HOST int32 (n_idx), copied to the device), the geometry, one batched 2D
+ * real-to-complex hipFFT of (nav_y, nav_x), min(max_batch, n_idx) bright-field pixels per execution, and its
+ * workspace: per pixel of a batch the float32 scan image, its complex64 half spectrum (nav_y, nav_x/2 + 1) and the
+ * transposed copy of that; plans of more than one batch also 40 bytes per Q for the sums so far.
+ * A scan of one row or one column is transformed by a batched 1D hipFFT.
+ * A non-positive scan or one of a single position, n_idx < 1, sig_w < 1, cutoff < 1, a non-finite geometry value, a
+ * non-positive lamb, dy, dx, semiconv or semiconv_pix, a batch of more than 2^31 - 1 values: LTMI_E_SHAPE; a null
+ * pointer, max_batch < 1: LTMI_E_INVALID. */
+typedef struct ltmi_ssb_plan ltmi_ssb_plan;   /* opaque */
+int ltmi_ssb_plan_create(int device, int nav_y, int nav_x, int sig_w, const int32_t *idx_host, int n_idx,
+                         int max_batch, const double *geom, int cutoff, ltmi_ssb_plan **out);
+int ltmi_ssb_plan_destroy(ltmi_ssb_plan *p);
+/* bf: device float32 (nav_y nav_x, n_idx), rows ld_bf elements apart (what ltmi_ssb_gather wrote for the whole scan);
+ * fourier_out: device complex64 (nav_y, nav_x), contiguous, the unshifted layout.  Per batch: ltmi_transpose2d (the
+ * batch's columns of bf -> one scan image per pixel), R2C, ltmi_transpose2d (spectra -> (Q, pixel)), k_ssb_trotter.
+ * Nothing is read back and the stream is not drained.  A pixel of bf that is not finite gives an unspecified result.
+ * ld_bf < n_idx: LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID. */
+int ltmi_ssb_reconstruct(ltmi_ssb_plan *p, const float *bf, int64_t ld_bf, void *fourier_out, void *stream);
+/* "k_transpose<4> + hipfft_r2c + k_transpose<8> + k_ssb_trotter batch=N" after the first ltmi_ssb_reconstruct call of
+ * this plan, "" before.  The string lives as long as the plan. */
+const char *ltmi_ssb_plan_last_kernel(const ltmi_ssb_plan *p);
+/* The last step alone, on half spectra the caller supplies: spec is DEVICE complex64, element
+ * spec[(iy (nav_x/2 + 1) + ix) ld_spec + K] = G[K, iy, ix] for ix <= nav_x / 2 (what a real-to-complex transform over
+ * the scan axes of bf viewed as (nav_y, nav_x, P) stores); a Q with ix > nav_x / 2 reads the conjugate at
+ * ((nav_y - iy) mod nav_y, nav_x - ix).  idx_dev: DEVICE int32 (n_idx) -- the indices give coordinates and never
+ * address memory.  One launch of k_ssb_trotter, one workgroup per Q.  Errors as for the plan, and ld_spec < n_idx:
+ * LTMI_E_SHAPE. */
+int ltmi_ssb_trotter(int device, const void *spec, int64_t ld_spec, int nav_y, int nav_x, const int32_t *idx_dev,
+                     int n_idx, int sig_w, const double *geom, int cutoff, void *fourier_out, void *stream);
+
 /* ---- lattice fit to the matched peaks -------------------------------------------------------------
  * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]
  * (1 where `weights` is NULL), integer lattice indices (i_k, j_k) = indices[k] (precondition |i|, |j| <= 2^20),

@@ -246,6 +246,10 @@ class HipJobExecutor(JobExecutor):
 
     def close(self):
         self._scattered = {}
+        if self.gpu_id is not None:
+            # the reconstruction plans SSBUDF.get_results cached for this device, with their workspace in HBM
+            from libertem_amd.udf import ssb
+            ssb.release_plans(self.gpu_id)
         if getattr(self, '_comm_state', None):
             self._comm_state.close()
             self._comm_state = None

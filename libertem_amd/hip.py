@@ -60,6 +60,8 @@ EXPORTS = (
     'ltmi_find_peaks_maps', 'ltmi_find_peaks_last_kernel', 'ltmi_correlate_find',
     'ltmi_holo_plan_create', 'ltmi_holo_plan_destroy', 'ltmi_holo_reconstruct', 'ltmi_holo_plan_last_kernel',
     'ltmi_holo_crop',
+    'ltmi_ssb_gather', 'ltmi_ssb_plan_create', 'ltmi_ssb_plan_destroy', 'ltmi_ssb_reconstruct',
+    'ltmi_ssb_plan_last_kernel', 'ltmi_ssb_trotter',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -356,6 +358,13 @@ def lib():
         L.ltmi_holo_plan_last_kernel.argtypes = [vp]
         L.ltmi_holo_plan_last_kernel.restype = c.c_char_p
         L.ltmi_holo_crop.argtypes = [i32, vp, i64, i32, i32, i64, i32, i32, i32, i32, vp, vp, i64, vp]
+        L.ltmi_ssb_gather.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, vp, i64, vp]
+        L.ltmi_ssb_plan_create.argtypes = [i32, i32, i32, i32, vp, i32, i32, vp, i32, c.POINTER(vp)]
+        L.ltmi_ssb_plan_destroy.argtypes = [vp]
+        L.ltmi_ssb_reconstruct.argtypes = [vp, vp, i64, vp, vp]
+        L.ltmi_ssb_plan_last_kernel.argtypes = [vp]
+        L.ltmi_ssb_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_ssb_trotter.argtypes = [i32, vp, i64, i32, i32, vp, i32, i32, vp, i32, vp, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -1125,6 +1134,80 @@ def holo_crop(device, spec_ptr, n_frames, h, w, ld_spec, out_h, out_w, sb_y, sb_
         int(device), spec_ptr, int(n_frames), int(h), int(w), int(ld_spec), int(out_h), int(out_w), int(sb_y),
         int(sb_x), aperture_ptr, g_ptr, int(ld_g), stream if isinstance(stream, int) else _stream_ptr(stream)),
         'ltmi_holo_crop')
+
+
+def ssb_geometry(lamb, dpix, semiconv, semiconv_pix, cy, cx, transformation):
+    """the `geom` array of the ltmi_ssb_* calls (include/ltmi.h): lamb, dy, dx, semiconv, semiconv_pix, cy, cx and the
+    2 x 2 transformation row by row, as 11 float64; dpix is (dy, dx)"""
+    t = np.asarray(transformation, dtype=np.float64).reshape(2, 2)
+    return np.array([lamb, dpix[0], dpix[1], semiconv, semiconv_pix, cy, cx, t[0, 0], t[0, 1], t[1, 0], t[1, 1]],
+                    dtype=np.float64)
+
+
+def ssb_gather(device, tile_ptr, tile_dtype, n_frames, ld_tile, n_px, idx_ptr, n_idx, out_ptr, ld_out, stream=None):
+    """The bright-field pixels of every frame of a tile: out[f, k] = float32(tile[f, idx[k]]).  tile: device
+    (n_frames, n_px) of tile_dtype, ld_tile elements apart; idx: device int32 (n_idx); out: device float32
+    (n_frames, n_idx), rows ld_out elements apart (include/ltmi.h)."""
+    check(lib().ltmi_ssb_gather(
+        int(device), tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), int(n_px), idx_ptr, int(n_idx),
+        out_ptr, int(ld_out), stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ssb_gather')
+
+
+class SSBPlan:
+    """Owns one `ltmi_ssb_plan*`: the bright-field list (host int32 frame indices), the geometry (`ssb_geometry`), the
+    cutoff, a batched 2D R2C hipFFT over the (nav_y, nav_x) scan for min(max_batch, P) bright-field pixels per
+    execution and its workspace."""
+
+    def __init__(self, device, nav_y, nav_x, sig_w, idx, max_batch, geom, cutoff):
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        geom = np.ascontiguousarray(geom, dtype=np.float64).reshape(-1)
+        if geom.size != 11:
+            raise ValueError(f"the geometry holds 11 values (hip.ssb_geometry), not {geom.size}")
+        out = ctypes.c_void_p()
+        check(lib().ltmi_ssb_plan_create(
+            int(device), int(nav_y), int(nav_x), int(sig_w), idx.ctypes.data_as(ctypes.c_void_p), int(idx.size),
+            int(max_batch), geom.ctypes.data_as(ctypes.c_void_p), int(cutoff), ctypes.byref(out)),
+            'ltmi_ssb_plan_create')
+        self._ptr = out
+        self.device, self.nav, self.n_idx = int(device), (int(nav_y), int(nav_x)), int(idx.size)
+        self.max_batch = int(max_batch)
+
+    def reconstruct(self, bf_ptr, ld_bf, fourier_ptr, stream=None):
+        """bf: device float32 (nav_y * nav_x, P), rows ld_bf elements apart; fourier: device complex64
+        (nav_y, nav_x), contiguous (include/ltmi.h)."""
+        check(lib().ltmi_ssb_reconstruct(
+            self._ptr, bf_ptr, int(ld_bf), fourier_ptr,
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ssb_reconstruct')
+
+    def last_kernel(self):
+        """'k_transpose<4> + hipfft_r2c + k_transpose<8> + k_ssb_trotter batch=N' after the first `reconstruct` call,
+        '' before"""
+        return lib().ltmi_ssb_plan_last_kernel(self._ptr).decode()
+
+    def close(self):
+        if self._ptr is not None and self._ptr.value:
+            lib().ltmi_ssb_plan_destroy(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ssb_trotter(device, spec_ptr, ld_spec, nav_y, nav_x, idx_ptr, n_idx, sig_w, geom, cutoff, fourier_ptr,
+                stream=None):
+    """The trotter sums of `SSBPlan.reconstruct` on complex64 half spectra the caller supplies: element
+    [(iy * (nav_x // 2 + 1) + ix) * ld_spec + k] is G[k, iy, ix]; idx: device int32 (n_idx); geom: `ssb_geometry`;
+    fourier: device complex64 (nav_y, nav_x) (include/ltmi.h)."""
+    geom = np.ascontiguousarray(geom, dtype=np.float64).reshape(-1)
+    if geom.size != 11:
+        raise ValueError(f"the geometry holds 11 values (hip.ssb_geometry), not {geom.size}")
+    check(lib().ltmi_ssb_trotter(
+        int(device), spec_ptr, int(ld_spec), int(nav_y), int(nav_x), idx_ptr, int(n_idx), int(sig_w),
+        geom.ctypes.data_as(ctypes.c_void_p), int(cutoff), fourier_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ssb_trotter')
 
 
 def lattice_fit(device, refineds_ptr, weights_ptr, peak_values_ptr, n_frames, n_peaks, indices_ptr, start, tolerance,

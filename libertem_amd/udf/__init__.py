@@ -9,11 +9,12 @@ from .record import RecordUDF
 from .correlation import CorrelationUDF, run_correlation
 from .peakfind import PeakFindUDF, run_peakfind, find_peaks, find_in_maps
 from .holography import HoloReconstructUDF, run_holo
+from .ssb import SSBUDF, run_ssb
 from .lattice import LatticeRefineUDF, run_refine, fit_lattice, lattice_peaks, lattice_strain
 
 __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPostprocessMixin', 'UDFPreprocessMixin',
            'UDFMergeAllMixin', 'UDFMeta', 'UDFRunner', 'UDFData', 'NoOpUDF', 'UDFMethod', 'check_cast', 'AutoUDF',
            'RecordUDF', 'CorrelationUDF', 'run_correlation', 'PeakFindUDF', 'run_peakfind', 'find_peaks', 'find_in_maps',
            'LatticeRefineUDF', 'run_refine', 'fit_lattice',
-           'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo',
+           'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb',
            'UDFRunCancelled', 'UDFException']

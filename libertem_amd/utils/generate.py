@@ -53,3 +53,54 @@ def hologram_frame(amp, phi, counts=1000., sampling=5., visibility=1., f_angle=3
         from scipy.ndimage import gaussian_filter
         holo = gaussian_filter(holo, gaussian_noise)
     return holo
+
+
+def weak_phase_scan(phi, step, semiconv_pix, counts=1000.):
+    """
+    A focused-probe 4D-STEM scan of the phase object exp(i phi) on a periodic grid: the frames
+    `libertem_amd.udf.ssb` reconstructs.
+
+    The probe is the inverse DFT of a top-hat aperture of radius `semiconv_pix` grid frequencies, normalised to
+    unit intensity.  Scan position (ry, rx) puts it on grid point (ry step, rx step): the exit wave is
+    probe[r] * obj[r + R] with wrap-around (a roll of the object), and the frame is counts * |DFT(exit)|^2 / (h w),
+    fftshifted, so that the bright-field disk has radius `semiconv_pix` around (h // 2, w // 2) and every frame sums
+    to `counts`.  No noise is added.
+
+    One detector pixel is one grid frequency, i.e. lamb / (h a) radians for a grid pixel of size a: a reconstruction
+    takes semiconv = semiconv_pix lamb / (h a), dpix = step a and the disk centre (h / 2, w / 2) (square grids; h and
+    w even), and returns phi sampled at the scan positions, phi[::step, ::step], up to its mean.
+
+    Parameters
+    ----------
+    phi : 2D array
+        phase of the object in rad, periodic; both edges are multiples of `step`
+    step : int
+        scan step in grid pixels
+    semiconv_pix : float
+        radius of the aperture in grid frequencies = detector pixels
+    counts : float
+        electrons per frame
+
+    Returns float64 frames of shape (h // step, w // step, h, w).
+    """
+    phi = np.asarray(phi, dtype=np.float64)
+    step = int(step)
+    if phi.ndim != 2:
+        raise ValueError(f"phi must be a 2D array, not shape {phi.shape}")
+    h, w = phi.shape
+    if step < 1 or h % step or w % step:
+        raise ValueError(f"step {step} must be positive and divide both edges of the {(h, w)} grid")
+    fy = np.fft.fftfreq(h, 1 / h)[:, None]
+    fx = np.fft.fftfreq(w, 1 / w)[None, :]
+    aperture = (fy * fy + fx * fx < float(semiconv_pix) ** 2).astype(np.float64)
+    if not aperture.any():
+        raise ValueError(f"an aperture of radius {semiconv_pix} holds no grid frequency")
+    probe = np.fft.ifft2(aperture)
+    probe /= np.sqrt((np.abs(probe) ** 2).sum())
+    obj = np.exp(1j * phi)
+    frames = np.empty((h // step, w // step, h, w), np.float64)
+    for ry in range(h // step):
+        for rx in range(w // step):
+            exit_wave = probe * np.roll(obj, (-ry * step, -rx * step), axis=(0, 1))
+            frames[ry, rx] = np.fft.fftshift(np.abs(np.fft.fft2(exit_wave)) ** 2) * (counts / (h * w))
+    return frames
