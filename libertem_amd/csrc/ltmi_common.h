@@ -110,7 +110,7 @@ static inline const char *dtype_name(int dt) {
 
 // One hipMalloc allocation and its owner: freed by the destructor, move-only; reads as the raw pointer it replaces
 // (kernel arguments, `if (buf)`, `buf + n`).  Counts are elements of T, bytes for DevBuf<void>.  The device of the
-// allocation must be current when the buffer goes (ltmi_masks_destroy and ltmi_fft_plan_destroy see to it).
+// allocation must be current when the buffer goes (ltmi_masks_destroy and plan_destroy of ltmi_fftshare.h see to it).
 template <typename T>
 class DevBuf {
     using E = typename std::conditional<std::is_void<T>::value, char, T>::type;

@@ -9,20 +9,16 @@
 // ltmi_peakfind.hip for the strongest local maxima of every map, rated by k_corr_found on the window code of k_corr_peaks.
 #include "ltmi_fftshare.h"
 #include <algorithm>
-#include <new>
 
 struct ltmi_corr_plan {
     int device = 0;
     int h = 0, w = 0, wc = 0;          // frame shape, complex columns w/2+1
     int batch = 0;                     // frames per hipFFT execution
-    hipfftHandle fwd = 0, inv = 0;
-    bool have_fwd = false, have_inv = false;
     ltmi::DevBuf<float> real_buf;      // (batch, h, w) f32: the frames, then their correlations
     ltmi::DevBuf<hipfftComplex> spec;  // (batch, h, wc) c64
     ltmi::DevBuf<hipfftComplex> tspec; // (h, wc): conj(rfft2(ifftshift(t))) / (h w)
     ltmi::DevBuf<uint64_t> cand;       // candidate keys of ltmi_correlate_find (ltmi_peakfind.hip), grown on demand
-    hipStream_t bound_stream = nullptr;
-    bool stream_bound = false;
+    ltmi::FftHandle fwd, inv;          // batched R2C and C2R
     char last_kernel[128] = {0};
 };
 
@@ -226,27 +222,10 @@ static int run_corr_load(const void *tile, int64_t ld, int64_t n, int64_t n_px, 
     return LTMI_OK;
 }
 
-bool corr_takes(int tile_dtype) {
-    switch (tile_dtype) {
-        case LTMI_BOOL: case LTMI_U8: case LTMI_I8: case LTMI_U16: case LTMI_I16: case LTMI_U32: case LTMI_I32:
-        case LTMI_F32: case LTMI_F64: return true;
-        default: return false;
-    }
-}
-
 int corr_load(const void *src, int tile_dtype, int64_t ld, int64_t n, int64_t n_px, float *out, hipStream_t stream) {
-    switch (tile_dtype) {
-        case LTMI_BOOL:
-        case LTMI_U8: return run_corr_load<uint8_t>(src, ld, n, n_px, out, stream);
-        case LTMI_I8: return run_corr_load<int8_t>(src, ld, n, n_px, out, stream);
-        case LTMI_U16: return run_corr_load<uint16_t>(src, ld, n, n_px, out, stream);
-        case LTMI_I16: return run_corr_load<int16_t>(src, ld, n, n_px, out, stream);
-        case LTMI_U32: return run_corr_load<uint32_t>(src, ld, n, n_px, out, stream);
-        case LTMI_I32: return run_corr_load<int32_t>(src, ld, n, n_px, out, stream);
-        case LTMI_F32: return run_corr_load<float>(src, ld, n, n_px, out, stream);
-        case LTMI_F64: return run_corr_load<double>(src, ld, n, n_px, out, stream);
-        default: LTMI_FAIL(LTMI_E_DTYPE, "k_corr_load: unsupported tile dtype %s", dtype_name(tile_dtype));
-    }
+    if (!corr_takes(tile_dtype)) LTMI_FAIL(LTMI_E_DTYPE, "k_corr_load: unsupported tile dtype %s", dtype_name(tile_dtype));
+    return visit_real_dtype(tile_dtype, [&](auto t) { return run_corr_load<decltype(t)>(src, ld, n, n_px, out, stream); },
+                            (int)LTMI_E_DTYPE);
 }
 
 static void corr_mul(ltmi_corr_plan *p, int64_t n, hipStream_t stream) {
@@ -265,13 +244,6 @@ static void corr_mul(ltmi_corr_plan *p, int64_t n, hipStream_t stream) {
 
 using namespace ltmi;
 
-static void corr_free(ltmi_corr_plan *p) {
-    (void)hipSetDevice(p->device);
-    if (p->have_fwd) (void)hipfftDestroy(p->fwd);
-    if (p->have_inv) (void)hipfftDestroy(p->inv);
-    delete p;
-}
-
 // the two hipFFT plans, the workspace and the template's spectrum
 static int corr_setup(ltmi_corr_plan *p, const float *template_host) {
     const int64_t n_px = (int64_t)p->h * p->w;
@@ -281,16 +253,9 @@ static int corr_setup(ltmi_corr_plan *p, const float *template_host) {
     if (e == hipSuccess) e = p->tspec.alloc((size_t)n_spec);
     if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_corr_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
     int n[2] = {p->h, p->w};
-    hipfftResult r = hipfftPlanMany(&p->fwd, 2, n, nullptr, 1, p->h * p->w, nullptr, 1, n_spec, HIPFFT_R2C, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(R2C %d x %d, batch %d) failed: %s", p->h, p->w, p->batch,
-                  fft_err(r));
-    p->have_fwd = true;
-    r = hipfftPlanMany(&p->inv, 2, n, nullptr, 1, n_spec, nullptr, 1, p->h * p->w, HIPFFT_C2R, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(C2R %d x %d, batch %d) failed: %s", p->h, p->w, p->batch,
-                  fft_err(r));
-    p->have_inv = true;
+    int rc = p->fwd.plan_many(2, n, p->h * p->w, n_spec, HIPFFT_R2C, p->batch);
+    if (rc == LTMI_OK) rc = p->inv.plan_many(2, n, n_spec, p->h * p->w, HIPFFT_C2R, p->batch);
+    if (rc != LTMI_OK) return rc;
     // ifftshift(t)[y, x] = t[(y + h/2) % h, (x + w/2) % w] as frame 0 of a zero batch, through the forward plan
     std::vector<float> shifted((size_t)n_px);
     for (int y = 0; y < p->h; ++y)
@@ -298,8 +263,8 @@ static int corr_setup(ltmi_corr_plan *p, const float *template_host) {
             shifted[(size_t)y * p->w + x] =
                 template_host[(size_t)((y + p->h / 2) % p->h) * p->w + (x + p->w / 2) % p->w];
     LTMI_HIP(hipMemcpy(p->real_buf, shifted.data(), (size_t)n_px * sizeof(float), hipMemcpyHostToDevice));
-    r = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
-    if (r != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(r));
+    rc = p->fwd.r2c(p->real_buf, p->spec);
+    if (rc != LTMI_OK) return rc;
     hipLaunchKernelGGL(k_corr_template, dim3((unsigned)((n_spec + 255) / 256)), dim3(256), 0, nullptr,
                        (const hipfftComplex *)p->spec, n_spec, (float)(1.0 / (double)n_px), (hipfftComplex *)p->tspec);
     LTMI_HIP(hipGetLastError());
@@ -314,62 +279,34 @@ extern "C" int ltmi_corr_plan_create(int device, int sig_h, int sig_w, int max_b
     if ((int64_t)max_batch * sig_h * sig_w > INT32_MAX)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_corr_plan_create: a batch of %d frames of %d x %d exceeds 2^31 - 1 pixels",
                   max_batch, sig_h, sig_w);
-    LTMI_HIP(hipSetDevice(device));
-    ltmi_corr_plan *p = new (std::nothrow) ltmi_corr_plan();
-    if (!p) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
-    p->device = device;
-    p->h = sig_h;
-    p->w = sig_w;
-    p->wc = sig_w / 2 + 1;
-    p->batch = max_batch;
-    const int rc = corr_setup(p, template_host);
-    if (rc != LTMI_OK) {
-        corr_free(p);
-        return rc;
-    }
-    *out = p;
-    return LTMI_OK;
+    return plan_create(device, out, [&](ltmi_corr_plan *p) {
+        p->h = sig_h;
+        p->w = sig_w;
+        p->wc = sig_w / 2 + 1;
+        p->batch = max_batch;
+        return corr_setup(p, template_host);
+    });
 }
 
-extern "C" int ltmi_corr_plan_destroy(ltmi_corr_plan *p) {
-    if (p) corr_free(p);
-    return LTMI_OK;
-}
+extern "C" int ltmi_corr_plan_destroy(ltmi_corr_plan *p) { return plan_destroy(p); }
 
 extern "C" const char *ltmi_corr_plan_last_kernel(const ltmi_corr_plan *p) {
     return p ? p->last_kernel : "";
 }
 
-// the plan's two transforms run on `stream` from here on
-static int corr_bind_stream(ltmi_corr_plan *p, hipStream_t stream) {
-    if (!p->stream_bound || p->bound_stream != stream) {
-        hipfftResult s = hipfftSetStream(p->fwd, stream);
-        if (s == HIPFFT_SUCCESS) s = hipfftSetStream(p->inv, stream);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(s));
-        p->bound_stream = stream;
-        p->stream_bound = true;
-    }
-    return LTMI_OK;
-}
-
-// n <= batch frames at `src` -> their correlation maps in real_buf: k_corr_load, R2C, k_corr_mul, C2R
-static int corr_transform(ltmi_corr_plan *p, const void *src, int tile_dtype, int64_t ld_tile, int64_t n,
+// frames [f0, f0 + n) of the tile, n <= batch -> their correlation maps in real_buf, on `stream`: k_corr_load, R2C,
+// k_corr_mul, C2R
+static int corr_transform(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t ld_tile, int64_t f0, int64_t n,
                           hipStream_t stream) {
-    const int64_t n_px = (int64_t)p->h * p->w;
-    const int rc = corr_load(src, tile_dtype, ld_tile, n, n_px, p->real_buf, stream);
+    int rc = p->fwd.bind(stream);
+    if (rc == LTMI_OK) rc = p->inv.bind(stream);
+    if (rc == LTMI_OK)
+        rc = load_and_forward(p->fwd, frame_at(tile, tile_dtype, ld_tile, f0), tile_dtype, ld_tile, n, p->batch,
+                              (int64_t)p->h * p->w, p->real_buf, p->spec, stream);
     if (rc != LTMI_OK) return rc;
-    if (n < p->batch) {
-        // the plans always transform `batch` frames: the unused tail holds zeros, not what an earlier batch
-        // left there (its transforms are never read)
-        LTMI_HIP(hipMemsetAsync(p->real_buf + n * n_px, 0, (size_t)(p->batch - n) * n_px * sizeof(float), stream));
-    }
-    hipfftResult s = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
-    if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(s));
     corr_mul(p, n, stream);
     LTMI_HIP(hipGetLastError());
-    s = hipfftExecC2R(p->inv, p->spec, p->real_buf);
-    if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecC2R failed: %s", fft_err(s));
-    return LTMI_OK;
+    return p->inv.c2r(p->spec, p->real_buf);
 }
 
 extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int tile_dtype, int64_t n_frames,
@@ -403,16 +340,11 @@ extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int til
     // (windows and neighbourhoods are clipped to the frame: a radius beyond its longer edge changes nothing)
     const int r = std::min(crop_radius, std::max(p->h, p->w));
     const int q = std::min(refine_radius, std::max(p->h, p->w));
-    const int rc_bind = corr_bind_stream(p, stream);
-    if (rc_bind != LTMI_OK) return rc_bind;
     snprintf(p->last_kernel, sizeof(p->last_kernel),
              "k_corr_load<%s> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=%d", dtype_name(tile_dtype),
              p->batch);
-    const size_t esz = (size_t)dtype_size(tile_dtype);
-    for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
-        const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
-        const void *src = (const char *)tile + (size_t)f0 * ld_tile * esz;
-        const int rc = corr_transform(p, src, tile_dtype, ld_tile, n, stream);
+    return for_each_batch(n_frames, p->batch, [&](int64_t f0, int64_t n) {
+        const int rc = corr_transform(p, tile, tile_dtype, ld_tile, f0, n, stream);
         if (rc != LTMI_OK) return rc;
         const int64_t waves = n * n_peaks;
         hipLaunchKernelGGL(k_corr_peaks, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream,
@@ -420,8 +352,8 @@ extern "C" int ltmi_correlate_peaks(ltmi_corr_plan *p, const void *tile, int til
                            centers + 2 * f0 * n_peaks, refineds + 2 * f0 * n_peaks, peak_values + f0 * n_peaks,
                            peak_elevations + f0 * n_peaks);
         LTMI_HIP(hipGetLastError());
-    }
-    return LTMI_OK;
+        return LTMI_OK;
+    });
 }
 
 // the statistics of the peaks a search found, for ltmi_peakfind.hip
@@ -454,20 +386,14 @@ extern "C" int ltmi_correlate_find(ltmi_corr_plan *p, const void *tile, int tile
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_correlate_find: null pointer");
     LTMI_HIP(hipSetDevice(p->device));
     hipStream_t stream = (hipStream_t)stream_;
-    rc = corr_bind_stream(p, stream);
-    if (rc != LTMI_OK) return rc;
     snprintf(p->last_kernel, sizeof(p->last_kernel),
              "k_corr_load<%s> + hipfft_r2c + k_corr_mul + hipfft_c2r + %s batch=%d", dtype_name(tile_dtype),
              peakfind_kernels(), p->batch);
-    const size_t esz = (size_t)dtype_size(tile_dtype);
     const int64_t N = pf.n_peaks;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
-        const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
-        rc = corr_transform(p, (const char *)tile + (size_t)f0 * ld_tile * esz, tile_dtype, ld_tile, n, stream);
+    return for_each_batch(n_frames, p->batch, [&](int64_t f0, int64_t n) {
+        const int rc = corr_transform(p, tile, tile_dtype, ld_tile, f0, n, stream);
         if (rc != LTMI_OK) return rc;
-        rc = peakfind_search(p->real_buf, n, p->h, p->w, n_px, pf, p->cand, n_found + f0, centers + 2 * f0 * N,
-                             refineds + 2 * f0 * N, peak_values + f0 * N, peak_elevations + f0 * N, stream);
-        if (rc != LTMI_OK) return rc;
-    }
-    return LTMI_OK;
+        return peakfind_search(p->real_buf, n, p->h, p->w, n_px, pf, p->cand, n_found + f0, centers + 2 * f0 * N,
+                               refineds + 2 * f0 * N, peak_values + f0 * N, peak_elevations + f0 * N, stream);
+    });
 }

@@ -8,22 +8,18 @@
 // plan's workspace.
 #include "ltmi_fftshare.h"
 #include <algorithm>
-#include <new>
 
 struct ltmi_fft_plan {
     int device = 0;
     int h = 0, w = 0, wc = 0;          // frame shape, complex columns w/2+1
     int batch = 0;                     // frames per hipFFT execution
-    hipfftHandle plan = 0;
-    bool have_plan = false;
     ltmi::DevBuf<float> real_buf;      // (batch, h, w) f32
     ltmi::DevBuf<hipfftComplex> spec;  // (batch, h, wc) c64
-    hipStream_t bound_stream = nullptr;
-    bool stream_bound = false;
     ltmi::DevBuf<float> mask_t;        // workspace of k_cryst_fused: both masks in lane order (ltmi_cryst.hip)
     ltmi::DevBuf<void> corr_ws;        // ... of the corrections inside its row stage: dark map, patch lists / values
     int n_cu = 0;
     bool fused_ok = false;             // 256 x 256 frames: k_cryst_fused (ltmi_cryst.hip) unless LTMI_FFT_FUSED=0
+    ltmi::FftHandle plan;              // batched R2C, created by the first call that needs it (hipfft_route_ready)
     char last_kernel[128] = {0};
 };
 
@@ -251,28 +247,15 @@ static int spec_ready(ltmi_fft_plan *p) {
     return LTMI_OK;
 }
 
-// the hipFFT plan + workspace of a plan, created on first use
+// the two workspaces + the hipFFT plan of a plan, created on first use; the plan last, so that a failed allocation
+// leaves none
 static int hipfft_route_ready(ltmi_fft_plan *p) {
-    if (p->have_plan) return LTMI_OK;
-    {
-        const int rc = real_buf_ready(p);
-        if (rc != LTMI_OK) return rc;
-    }
+    if (p->plan) return LTMI_OK;
+    int rc = real_buf_ready(p);
+    if (rc == LTMI_OK) rc = spec_ready(p);
+    if (rc != LTMI_OK) return rc;
     int n[2] = {p->h, p->w};
-    hipfftResult r = hipfftPlanMany(&p->plan, 2, n, nullptr, 1, p->h * p->w, nullptr, 1, p->h * p->wc,
-                                    HIPFFT_R2C, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(%d x %d, batch %d) failed: %s", p->h, p->w, p->batch,
-                  fft_err(r));
-    {
-        const int rc = spec_ready(p);
-        if (rc != LTMI_OK) {
-            (void)hipfftDestroy(p->plan);
-            return rc;
-        }
-    }
-    p->have_plan = true;
-    return LTMI_OK;
+    return p->plan.plan_many(2, n, p->h * p->w, p->h * p->wc, HIPFFT_R2C, p->batch);
 }
 
 extern "C" int ltmi_fft_plan_create(int device, int sig_h, int sig_w, int max_batch,
@@ -280,44 +263,25 @@ extern "C" int ltmi_fft_plan_create(int device, int sig_h, int sig_w, int max_ba
     if (!out || sig_h <= 0 || sig_w <= 0 || max_batch <= 0)
         LTMI_FAIL(LTMI_E_INVALID, "ltmi_fft_plan_create: bad arguments (%d x %d, batch %d)", sig_h,
                   sig_w, max_batch);
-    LTMI_HIP(hipSetDevice(device));
-    ltmi_fft_plan *p = new (std::nothrow) ltmi_fft_plan();
-    if (!p) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
-    p->device = device;
-    p->h = sig_h;
-    p->w = sig_w;
-    p->wc = sig_w / 2 + 1;
-    p->batch = max_batch;
-    hipError_t e = hipSuccess;
-    if (cryst_fused_shape(sig_h, sig_w)) {
-        p->fused_ok = !switch_is<LTMI_FFT_FUSED>('0');
-        e = p->mask_t.alloc((size_t)cryst_fused_workspace_floats(sig_h, sig_w));
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) {
-            delete p;
-            LTMI_FAIL((int)e, "ltmi_fft_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
+    return plan_create(device, out, [&](ltmi_fft_plan *p) {
+        p->h = sig_h;
+        p->w = sig_w;
+        p->wc = sig_w / 2 + 1;
+        p->batch = max_batch;
+        if (cryst_fused_shape(sig_h, sig_w)) {
+            p->fused_ok = !switch_is<LTMI_FFT_FUSED>('0');
+            hipError_t e = p->mask_t.alloc((size_t)cryst_fused_workspace_floats(sig_h, sig_w));
+            if (e == hipSuccess) e = hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, device);
+            if (e != hipSuccess)
+                LTMI_FAIL((int)e, "ltmi_fft_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
         }
-    }
-    // frames the fused kernel takes never need the hipFFT plan and its (batch x frame) workspace: both are
-    // created by the first call that does (hipfft_route_ready)
-    if (!p->fused_ok) {
-        const int rc = hipfft_route_ready(p);
-        if (rc != LTMI_OK) {
-            delete p;
-            return rc;
-        }
-    }
-    *out = p;
-    return LTMI_OK;
+        // frames the fused kernel takes never need the hipFFT plan and its (batch x frame) workspace: both are
+        // created by the first call that does (hipfft_route_ready)
+        return p->fused_ok ? LTMI_OK : hipfft_route_ready(p);
+    });
 }
 
-extern "C" int ltmi_fft_plan_destroy(ltmi_fft_plan *p) {
-    if (!p) return LTMI_OK;
-    (void)hipSetDevice(p->device);
-    if (p->have_plan) (void)hipfftDestroy(p->plan);
-    delete p;
-    return LTMI_OK;
-}
+extern "C" int ltmi_fft_plan_destroy(ltmi_fft_plan *p) { return plan_destroy(p); }
 
 extern "C" const char *ltmi_fft_plan_last_kernel(const ltmi_fft_plan *p) {
     return p ? p->last_kernel : "";
@@ -385,7 +349,6 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
     if (!tile || !half_mask || !out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_crystallinity: null pointer");
     LTMI_HIP(hipSetDevice(p->device));
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t esz = (size_t)dtype_size(tile_dtype);
     if (row_lo < 0 || row_hi < row_lo || row_hi > p->h || n_cols < 0 || n_cols > p->wc)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_crystallinity: bad mask bounding box (%d, %d, %d)", row_lo,
                   row_hi, n_cols);
@@ -427,7 +390,7 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
         for (int64_t f0 = 0; f0 < n_frames && all; f0 += chunk) {
             const int64_t n = std::min(chunk, n_frames - f0);
             bool handled = false;
-            const int rc = cryst_fused_corrected((const char *)tile + (size_t)f0 * ld_tile * esz, tile_dtype, n, ld_tile,
+            const int rc = cryst_fused_corrected(frame_at(tile, tile_dtype, ld_tile, f0), tile_dtype, n, ld_tile,
                                                  p->h, p->w, corr.dark, corr.gain, corr.excl, corr.env, corr.cnt,
                                                  corr.n_excl, corr.max_env, real_mask, half_mask, n_cols, p->mask_t,
                                                  p->spec, p->batch, p->corr_ws, out + f0, accumulate, p->n_cu, stream,
@@ -458,17 +421,18 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
             const int rc1 = spec_ready(p);
             if (rc1 != LTMI_OK) return rc1;
         }
-        for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
-            const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
-            const void *src = (const char *)tile + (size_t)f0 * ld_tile * esz;
-            int rc = prepare_batch(p, src, tile_dtype, ld_tile, n, n_px, real_mask, stream, corr);
+        const int rc_all = for_each_batch(n_frames, p->batch, [&](int64_t f0, int64_t n) {
+            int rc = prepare_batch(p, frame_at(tile, tile_dtype, ld_tile, f0), tile_dtype, ld_tile, n, n_px, real_mask,
+                                   stream, corr);
             if (rc != LTMI_OK) return rc;
             bool handled = false;
             rc = cryst_fused(p->real_buf, LTMI_F32, n, n_px, p->h, p->w, nullptr, half_mask, n_cols, p->mask_t,
                              p->spec, p->batch, out + f0, accumulate, p->n_cu, stream, &handled);
             if (rc != LTMI_OK) return rc;
             if (!handled) LTMI_FAIL(LTMI_E_INVALID, "ltmi_crystallinity: the fused kernel refused its own workspace");
-        }
+            return LTMI_OK;
+        });
+        if (rc_all != LTMI_OK) return rc_all;
         if (cryst_fused_needs_gbuf(p->h, p->w, n_cols))
             snprintf(p->last_kernel, sizeof(p->last_kernel), "k_fft_prepare<%s> + k_cryst_rows%d<float32> + k_cryst_cols%d columns=%d",
                      dtype_name(tile_dtype), p->w, p->h, n_cols);
@@ -479,33 +443,19 @@ static int crystallinity_impl(ltmi_fft_plan *p, const void *tile, int tile_dtype
     }
     snprintf(p->last_kernel, sizeof(p->last_kernel), "hipfft_r2c<%s> batch=%d", dtype_name(tile_dtype),
              p->batch);
-    {
-        const int rc = hipfft_route_ready(p);
+    int rc_ready = hipfft_route_ready(p);
+    if (rc_ready == LTMI_OK) rc_ready = p->plan.bind(stream);
+    if (rc_ready != LTMI_OK) return rc_ready;
+    return for_each_batch(n_frames, p->batch, [&](int64_t f0, int64_t n) {
+        int rc = prepare_batch(p, frame_at(tile, tile_dtype, ld_tile, f0), tile_dtype, ld_tile, n, n_px, real_mask,
+                               stream, corr);
+        if (rc == LTMI_OK) rc = zero_tail(p->real_buf, n, p->batch, n_px, stream);
+        if (rc == LTMI_OK) rc = p->plan.r2c(p->real_buf, p->spec);
         if (rc != LTMI_OK) return rc;
-    }
-    if (!p->stream_bound || p->bound_stream != stream) {
-        hipfftResult r = hipfftSetStream(p->plan, stream);
-        if (r != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(r));
-        p->bound_stream = stream;
-        p->stream_bound = true;
-    }
-    for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
-        const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
-        const void *src = (const char *)tile + (size_t)f0 * ld_tile * esz;
-        const int rc = prepare_batch(p, src, tile_dtype, ld_tile, n, n_px, real_mask, stream, corr);
-        if (rc != LTMI_OK) return rc;
-        if (n < p->batch) {
-            // the plan always transforms `batch` frames: clear the unused tail once so that it
-            // holds finite numbers (its spectra are never read)
-            LTMI_HIP(hipMemsetAsync(p->real_buf + n * n_px, 0,
-                                    (size_t)(p->batch - n) * n_px * sizeof(float), stream));
-        }
-        hipfftResult r = hipfftExecR2C(p->plan, p->real_buf, p->spec);
-        if (r != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(r));
         hipLaunchKernelGGL(k_abs_dot, dim3((unsigned)n), dim3(256), 0, stream,
                            (const hipfftComplex *)p->spec, p->h, p->wc, half_mask, row_lo, row_hi,
                            n_cols, out + f0, accumulate);
         LTMI_HIP(hipGetLastError());
-    }
-    return LTMI_OK;
+        return LTMI_OK;
+    });
 }

@@ -7,7 +7,6 @@
 // and Hermitian mirroring), hipFFT C2C backward in place, k_holo_store.  No atomics: a second call gives the same bytes.
 #include "ltmi_fftshare.h"
 #include <algorithm>
-#include <new>
 
 struct ltmi_holo_plan {
     int device = 0;
@@ -15,15 +14,12 @@ struct ltmi_holo_plan {
     int oh = 0, ow = 0;                 // output shape
     int sy = 0, sx = 0;                 // the sideband in the unshifted fft2 layout
     int batch = 0;                      // frames per hipFFT execution
-    hipfftHandle fwd = 0, inv = 0;
-    bool have_fwd = false, have_inv = false;
     ltmi::DevBuf<float> real_buf;       // (batch, h, w) f32
     ltmi::DevBuf<hipfftComplex> spec;   // (batch, h, wc) c64
     ltmi::DevBuf<hipfftComplex> work;   // (batch, oh, ow) c64: the cropped sideband, then the wave
     ltmi::DevBuf<float> aperture;       // (oh, ow): float32(aperture / (h w))
     ltmi::DevBuf<hipfftComplex> ref_inv;   // (oh, ow): 1 / reference_wave, or none
-    hipStream_t bound_stream = nullptr;
-    bool stream_bound = false;
+    ltmi::FftHandle fwd, inv;           // batched R2C of (h, w), batched C2C of (oh, ow)
     char last_kernel[128] = {0};
 };
 
@@ -102,13 +98,6 @@ static int holo_check_shapes(const char *who, int h, int w, int oh, int ow, int 
 
 using namespace ltmi;
 
-static void holo_free(ltmi_holo_plan *p) {
-    (void)hipSetDevice(p->device);
-    if (p->have_fwd) (void)hipfftDestroy(p->fwd);
-    if (p->have_inv) (void)hipfftDestroy(p->inv);
-    delete p;
-}
-
 // the two hipFFT plans, the workspaces, the scaled aperture and the inverse reference
 static int holo_setup(ltmi_holo_plan *p, const float *aperture_host, const float *ref_inv_host) {
     const int64_t n_px = (int64_t)p->h * p->w;
@@ -123,18 +112,9 @@ static int holo_setup(ltmi_holo_plan *p, const float *aperture_host, const float
     if (e == hipSuccess && ref_inv_host) e = p->ref_inv.upload((const hipfftComplex *)ref_inv_host, (size_t)n_out);
     if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_holo_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
     int n[2] = {p->h, p->w};
-    hipfftResult r = hipfftPlanMany(&p->fwd, 2, n, nullptr, 1, p->h * p->w, nullptr, 1, n_spec, HIPFFT_R2C, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(R2C %d x %d, batch %d) failed: %s", p->h, p->w, p->batch,
-                  fft_err(r));
-    p->have_fwd = true;
     int m[2] = {p->oh, p->ow};                  // (hipFFT takes axes of one element, a 1 x 1 output included)
-    r = hipfftPlanMany(&p->inv, 2, m, nullptr, 1, n_out, nullptr, 1, n_out, HIPFFT_C2C, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(C2C %d x %d, batch %d) failed: %s", p->oh, p->ow, p->batch,
-                  fft_err(r));
-    p->have_inv = true;
-    return LTMI_OK;
+    const int rc = p->fwd.plan_many(2, n, p->h * p->w, n_spec, HIPFFT_R2C, p->batch);
+    return rc == LTMI_OK ? p->inv.plan_many(2, m, n_out, n_out, HIPFFT_C2C, p->batch) : rc;
 }
 
 extern "C" int ltmi_holo_plan_create(int device, int sig_h, int sig_w, int out_h, int out_w, int max_batch, int sb_y,
@@ -147,31 +127,20 @@ extern "C" int ltmi_holo_plan_create(int device, int sig_h, int sig_w, int out_h
     if ((int64_t)max_batch * sig_h * sig_w > INT32_MAX)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_holo_plan_create: a batch of %d frames of %d x %d exceeds 2^31 - 1 pixels",
                   max_batch, sig_h, sig_w);
-    LTMI_HIP(hipSetDevice(device));
-    ltmi_holo_plan *p = new (std::nothrow) ltmi_holo_plan();
-    if (!p) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
-    p->device = device;
-    p->h = sig_h;
-    p->w = sig_w;
-    p->wc = sig_w / 2 + 1;
-    p->oh = out_h;
-    p->ow = out_w;
-    p->sy = sb_y;
-    p->sx = sb_x;
-    p->batch = max_batch;
-    const int rc = holo_setup(p, aperture_host, ref_inv_host);
-    if (rc != LTMI_OK) {
-        holo_free(p);
-        return rc;
-    }
-    *out = p;
-    return LTMI_OK;
+    return plan_create(device, out, [&](ltmi_holo_plan *p) {
+        p->h = sig_h;
+        p->w = sig_w;
+        p->wc = sig_w / 2 + 1;
+        p->oh = out_h;
+        p->ow = out_w;
+        p->sy = sb_y;
+        p->sx = sb_x;
+        p->batch = max_batch;
+        return holo_setup(p, aperture_host, ref_inv_host);
+    });
 }
 
-extern "C" int ltmi_holo_plan_destroy(ltmi_holo_plan *p) {
-    if (p) holo_free(p);
-    return LTMI_OK;
-}
+extern "C" int ltmi_holo_plan_destroy(ltmi_holo_plan *p) { return plan_destroy(p); }
 
 extern "C" const char *ltmi_holo_plan_last_kernel(const ltmi_holo_plan *p) {
     return p ? p->last_kernel : "";
@@ -191,34 +160,20 @@ extern "C" int ltmi_holo_reconstruct(ltmi_holo_plan *p, const void *tile, int ti
     if (!tile || !out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_holo_reconstruct: null pointer");
     LTMI_HIP(hipSetDevice(p->device));
     hipStream_t stream = (hipStream_t)stream_;
-    if (!p->stream_bound || p->bound_stream != stream) {
-        hipfftResult s = hipfftSetStream(p->fwd, stream);
-        if (s == HIPFFT_SUCCESS) s = hipfftSetStream(p->inv, stream);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(s));
-        p->bound_stream = stream;
-        p->stream_bound = true;
-    }
+    int rc_bind = p->fwd.bind(stream);
+    if (rc_bind == LTMI_OK) rc_bind = p->inv.bind(stream);
+    if (rc_bind != LTMI_OK) return rc_bind;
     snprintf(p->last_kernel, sizeof(p->last_kernel),
              "k_corr_load<%s> + hipfft_r2c + k_holo_crop + hipfft_c2c + k_holo_store batch=%d", dtype_name(tile_dtype),
              p->batch);
-    const size_t esz = (size_t)dtype_size(tile_dtype);
-    for (int64_t f0 = 0; f0 < n_frames; f0 += p->batch) {
-        const int64_t n = std::min<int64_t>(p->batch, n_frames - f0);
-        int rc = corr_load((const char *)tile + (size_t)f0 * ld_tile * esz, tile_dtype, ld_tile, n, n_px, p->real_buf,
-                           stream);
+    return for_each_batch(n_frames, p->batch, [&](int64_t f0, int64_t n) {
+        int rc = load_and_forward(p->fwd, frame_at(tile, tile_dtype, ld_tile, f0), tile_dtype, ld_tile, n, p->batch, n_px,
+                                  p->real_buf, p->spec, stream);
+        if (rc == LTMI_OK)
+            rc = holo_crop_launch(p->spec, (int64_t)p->h * p->wc, n, p->h, p->w, p->oh, p->ow, p->sy, p->sx,
+                                  p->aperture, p->work, n_out, stream);
+        if (rc == LTMI_OK) rc = p->inv.c2c(p->work, p->work, HIPFFT_BACKWARD);
         if (rc != LTMI_OK) return rc;
-        if (n < p->batch) {
-            // the plans always transform `batch` frames: the unused tail holds zeros, not what an earlier batch
-            // left there (its transforms are never read)
-            LTMI_HIP(hipMemsetAsync(p->real_buf + n * n_px, 0, (size_t)(p->batch - n) * n_px * sizeof(float), stream));
-        }
-        hipfftResult s = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(s));
-        rc = holo_crop_launch(p->spec, (int64_t)p->h * p->wc, n, p->h, p->w, p->oh, p->ow, p->sy, p->sx, p->aperture,
-                              p->work, n_out, stream);
-        if (rc != LTMI_OK) return rc;
-        s = hipfftExecC2C(p->inv, p->work, p->work, HIPFFT_BACKWARD);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecC2C failed: %s", fft_err(s));
         float2 *dst = (float2 *)out + f0 * ld_out;
         if (p->ref_inv)
             hipLaunchKernelGGL(k_holo_store<true>, holo_grid(n_out, n), dim3(256), 0, stream,
@@ -227,8 +182,8 @@ extern "C" int ltmi_holo_reconstruct(ltmi_holo_plan *p, const void *tile, int ti
             hipLaunchKernelGGL(k_holo_store<false>, holo_grid(n_out, n), dim3(256), 0, stream,
                                (const float2 *)p->work.get(), n_out, n, (const float2 *)nullptr, dst, ld_out);
         LTMI_HIP(hipGetLastError());
-    }
-    return LTMI_OK;
+        return LTMI_OK;
+    });
 }
 
 extern "C" int ltmi_holo_crop(int device, const void *spec, int64_t n_frames, int h, int w, int64_t ld_spec, int out_h,

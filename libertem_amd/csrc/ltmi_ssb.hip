@@ -10,7 +10,6 @@
 #include "ltmi_fftshare.h"
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 // the three disk predicates agree with a NumPy float64 evaluation of the same expressions bit for bit: every product
 // and sum below is rounded on its own
@@ -206,23 +205,14 @@ struct ltmi_ssb_plan {
     int n_idx = 0;                      // P
     int batch = 0;                      // bright-field pixels per hipFFT execution
     SsbGeom g = {};
-    hipfftHandle fwd = 0;
-    bool have_fwd = false;
     DevBuf<int32_t> idx;                // (P): the bright-field list
     DevBuf<float> real_buf;             // (batch, ny, nx) f32: one scan image per bright-field pixel
     DevBuf<hipfftComplex> spec;         // (batch, ny, nxc) c64
     DevBuf<hipfftComplex> spec_t;       // (ny nxc, batch) c64: the same, a Q's pixels contiguous
     DevBuf<SsbAcc> acc;                 // (ny nx): the sums of the batches so far (plans of more than one batch)
-    hipStream_t bound_stream = nullptr;
-    bool stream_bound = false;
+    FftHandle fwd;                      // batched R2C over the scan axes
     char last_kernel[128] = {0};
 };
-
-static void ssb_free(ltmi_ssb_plan *p) {
-    (void)hipSetDevice(p->device);
-    if (p->have_fwd) (void)hipfftDestroy(p->fwd);
-    delete p;
-}
 
 static int ssb_setup(ltmi_ssb_plan *p, const int32_t *idx_host) {
     const int64_t n_nav = (int64_t)p->g.ny * p->g.nx;
@@ -234,14 +224,8 @@ static int ssb_setup(ltmi_ssb_plan *p, const int32_t *idx_host) {
     if (e == hipSuccess && p->batch < p->n_idx) e = p->acc.alloc_zero((size_t)n_nav);
     if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_ssb_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
     int n[2] = {p->g.ny, p->g.nx};              // a line scan is a batch of 1D transforms
-    const hipfftResult r = p->g.ny == 1
-        ? hipfftPlanMany(&p->fwd, 1, n + 1, nullptr, 1, (int)n_nav, nullptr, 1, n_spec, HIPFFT_R2C, p->batch)
-        : hipfftPlanMany(&p->fwd, 2, n, nullptr, 1, (int)n_nav, nullptr, 1, n_spec, HIPFFT_R2C, p->batch);
-    if (r != HIPFFT_SUCCESS)
-        LTMI_FAIL(LTMI_E_INVALID, "hipfftPlanMany(R2C %d x %d, batch %d) failed: %s", p->g.ny, p->g.nx, p->batch,
-                  fft_err(r));
-    p->have_fwd = true;
-    return LTMI_OK;
+    return p->g.ny == 1 ? p->fwd.plan_many(1, n + 1, (int)n_nav, n_spec, HIPFFT_R2C, p->batch)
+                        : p->fwd.plan_many(2, n, (int)n_nav, n_spec, HIPFFT_R2C, p->batch);
 }
 
 extern "C" int ltmi_ssb_gather(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
@@ -257,17 +241,9 @@ extern "C" int ltmi_ssb_gather(int device, const void *tile, int tile_dtype, int
     if (!tile || !idx_dev || !out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_ssb_gather: null pointer");
     LTMI_HIP(hipSetDevice(device));
     hipStream_t stream = (hipStream_t)stream_;
-    switch (tile_dtype) {
-        case LTMI_BOOL:
-        case LTMI_U8: return run_ssb_gather<uint8_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_I8: return run_ssb_gather<int8_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_U16: return run_ssb_gather<uint16_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_I16: return run_ssb_gather<int16_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_U32: return run_ssb_gather<uint32_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_I32: return run_ssb_gather<int32_t>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        case LTMI_F32: return run_ssb_gather<float>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-        default: return run_ssb_gather<double>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
-    }
+    return visit_real_dtype(tile_dtype, [&](auto t) {
+        return run_ssb_gather<decltype(t)>(tile, ld_tile, n_frames, n_px, idx_dev, n_idx, out, ld_out, stream);
+    }, (int)LTMI_E_DTYPE);                      // (corr_takes above: never)
 }
 
 extern "C" int ltmi_ssb_plan_create(int device, int nav_y, int nav_x, int sig_w, const int32_t *idx_host, int n_idx,
@@ -290,26 +266,15 @@ extern "C" int ltmi_ssb_plan_create(int device, int nav_y, int nav_x, int sig_w,
     if ((int64_t)batch * nav_y * nav_x > INT32_MAX)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_ssb_plan_create: a batch of %d scans of %d x %d exceeds 2^31 - 1 values", batch,
                   nav_y, nav_x);
-    LTMI_HIP(hipSetDevice(device));
-    ltmi_ssb_plan *p = new (std::nothrow) ltmi_ssb_plan();
-    if (!p) LTMI_FAIL(LTMI_E_NOMEM, "out of host memory");
-    p->device = device;
-    p->n_idx = n_idx;
-    p->batch = batch;
-    p->g = g;
-    const int rc = ssb_setup(p, idx_host);
-    if (rc != LTMI_OK) {
-        ssb_free(p);
-        return rc;
-    }
-    *out = p;
-    return LTMI_OK;
+    return plan_create(device, out, [&](ltmi_ssb_plan *p) {
+        p->n_idx = n_idx;
+        p->batch = batch;
+        p->g = g;
+        return ssb_setup(p, idx_host);
+    });
 }
 
-extern "C" int ltmi_ssb_plan_destroy(ltmi_ssb_plan *p) {
-    if (p) ssb_free(p);
-    return LTMI_OK;
-}
+extern "C" int ltmi_ssb_plan_destroy(ltmi_ssb_plan *p) { return plan_destroy(p); }
 
 extern "C" const char *ltmi_ssb_plan_last_kernel(const ltmi_ssb_plan *p) {
     return p ? p->last_kernel : "";
@@ -322,31 +287,23 @@ extern "C" int ltmi_ssb_reconstruct(ltmi_ssb_plan *p, const float *bf, int64_t l
     if (!bf || !fourier_out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_ssb_reconstruct: null pointer");
     LTMI_HIP(hipSetDevice(p->device));
     hipStream_t stream = (hipStream_t)stream_;
-    if (!p->stream_bound || p->bound_stream != stream) {
-        const hipfftResult s = hipfftSetStream(p->fwd, stream);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftSetStream failed: %s", fft_err(s));
-        p->bound_stream = stream;
-        p->stream_bound = true;
-    }
+    const int rc_bind = p->fwd.bind(stream);
+    if (rc_bind != LTMI_OK) return rc_bind;
     snprintf(p->last_kernel, sizeof(p->last_kernel), "k_transpose<4> + hipfft_r2c + k_transpose<8> + k_ssb_trotter batch=%d",
              p->batch);
     const int64_t n_nav = (int64_t)p->g.ny * p->g.nx;
     const int64_t n_spec = (int64_t)p->g.ny * (p->g.nx / 2 + 1);
-    for (int k0 = 0; k0 < p->n_idx; k0 += p->batch) {
-        const int n = std::min(p->batch, p->n_idx - k0);
+    // the batches are bright-field pixels here
+    return for_each_batch(p->n_idx, p->batch, [&](int64_t k0, int64_t n) {
         // column k of bf = the scan image of bright-field pixel k; the plan always transforms `batch` images: a
         // partial last batch leaves the images of an earlier one in the tail, whose spectra are never read
         int rc = ltmi_transpose2d(p->device, bf + k0, ld_bf, n_nav, n, 4, p->real_buf, n_nav, stream_);
+        if (rc == LTMI_OK) rc = p->fwd.r2c(p->real_buf, p->spec);
+        if (rc == LTMI_OK) rc = ltmi_transpose2d(p->device, p->spec, n_spec, n, n_spec, 8, p->spec_t, p->batch, stream_);
         if (rc != LTMI_OK) return rc;
-        const hipfftResult s = hipfftExecR2C(p->fwd, p->real_buf, p->spec);
-        if (s != HIPFFT_SUCCESS) LTMI_FAIL(LTMI_E_INVALID, "hipfftExecR2C failed: %s", fft_err(s));
-        rc = ltmi_transpose2d(p->device, p->spec, n_spec, n, n_spec, 8, p->spec_t, p->batch, stream_);
-        if (rc != LTMI_OK) return rc;
-        rc = ssb_trotter_launch(p->spec_t, p->batch, p->idx + k0, n, p->g, p->acc, k0 == 0, k0 + n == p->n_idx,
-                                (hipfftComplex *)fourier_out, stream);
-        if (rc != LTMI_OK) return rc;
-    }
-    return LTMI_OK;
+        return ssb_trotter_launch(p->spec_t, p->batch, p->idx + k0, (int)n, p->g, p->acc, k0 == 0, k0 + n == p->n_idx,
+                                  (hipfftComplex *)fourier_out, stream);
+    });
 }
 
 extern "C" int ltmi_ssb_trotter(int device, const void *spec, int64_t ld_spec, int nav_y, int nav_x,

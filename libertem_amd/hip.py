@@ -951,8 +951,30 @@ def com_fields(device, raw_ptr, ld_raw, ny, nx, ref_y, ref_x, transform, out_y, 
         'ltmi_com_fields')
 
 
-class FFTPlan:
+class _NativePlan:
+    """What the owners of a native plan share: `_ptr` (set by the subclass's constructor, None once closed) and the
+    library's functions named `_destroy` and `_last_kernel`."""
+    _ptr = None
+    _destroy = _last_kernel = None
+
+    def last_kernel(self):
+        return getattr(lib(), self._last_kernel)(self._ptr).decode()
+
+    def close(self):
+        if self._ptr is not None and self._ptr.value:
+            getattr(lib(), self._destroy)(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FFTPlan(_NativePlan):
     """Owns one `ltmi_fft_plan*`: batched 2D R2C hipFFT + workspace for frames of (sig_h, sig_w)."""
+    _destroy, _last_kernel = 'ltmi_fft_plan_destroy', 'ltmi_fft_plan_last_kernel'
 
     def __init__(self, device, sig_h, sig_w, max_batch):
         out = ctypes.c_void_p()
@@ -986,23 +1008,13 @@ class FFTPlan:
 
     def last_kernel(self):
         """'k_cryst_fused<...>' or 'hipfft_r2c<...>': the route of the last crystallinity call"""
-        return lib().ltmi_fft_plan_last_kernel(self._ptr).decode()
-
-    def close(self):
-        if self._ptr is not None and self._ptr.value:
-            lib().ltmi_fft_plan_destroy(self._ptr)
-            self._ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().last_kernel()
 
 
-class CorrPlan:
+class CorrPlan(_NativePlan):
     """Owns one `ltmi_corr_plan*`: batched 2D R2C and C2R hipFFTs + workspace for frames of (sig_h, sig_w), and the
     device spectrum of one template (host float32 (sig_h, sig_w), centred at (sig_h // 2, sig_w // 2))."""
+    _destroy, _last_kernel = 'ltmi_corr_plan_destroy', 'ltmi_corr_plan_last_kernel'
 
     def __init__(self, device, sig_h, sig_w, max_batch, template):
         t = np.ascontiguousarray(template, dtype=np.float32)
@@ -1041,18 +1053,7 @@ class CorrPlan:
     def last_kernel(self):
         """'k_corr_load<...> + hipfft_r2c + k_corr_mul + hipfft_c2r + k_corr_peaks batch=N'; after `find_peaks` the
         search kernels 'k_pf_cells + k_pf_verify + k_pf_select + k_corr_found' stand in place of k_corr_peaks"""
-        return lib().ltmi_corr_plan_last_kernel(self._ptr).decode()
-
-    def close(self):
-        if self._ptr is not None and self._ptr.value:
-            lib().ltmi_corr_plan_destroy(self._ptr)
-            self._ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().last_kernel()
 
 
 def find_peaks_maps(device, maps_ptr, n_frames, h, w, ld_map, num_peaks, min_distance, border, threshold_abs,
@@ -1073,11 +1074,12 @@ def find_peaks_last_kernel():
     return lib().ltmi_find_peaks_last_kernel().decode()
 
 
-class HoloPlan:
+class HoloPlan(_NativePlan):
     """Owns one `ltmi_holo_plan*`: a batched 2D R2C hipFFT of (sig_h, sig_w), a batched backward C2C hipFFT of
     (out_h, out_w) and their workspace, the sideband position (sb_y, sb_x) in the unshifted fft2 layout, the real
     aperture (host float32 (out_h, out_w), unshifted layout, (0, 0) the sideband centre) and, optionally, a complex
     reference wave of the same shape, inverted here in complex128 and stored as complex64."""
+    _destroy, _last_kernel = 'ltmi_holo_plan_destroy', 'ltmi_holo_plan_last_kernel'
 
     def __init__(self, device, sig_h, sig_w, out_h, out_w, max_batch, sb_y, sb_x, aperture, reference_wave=None):
         out_shape = (int(out_h), int(out_w))
@@ -1111,18 +1113,7 @@ class HoloPlan:
     def last_kernel(self):
         """'k_corr_load<...> + hipfft_r2c + k_holo_crop + hipfft_c2c + k_holo_store batch=N' after the first launching
         `reconstruct` call, '' before"""
-        return lib().ltmi_holo_plan_last_kernel(self._ptr).decode()
-
-    def close(self):
-        if self._ptr is not None and self._ptr.value:
-            lib().ltmi_holo_plan_destroy(self._ptr)
-            self._ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().last_kernel()
 
 
 def holo_crop(device, spec_ptr, n_frames, h, w, ld_spec, out_h, out_w, sb_y, sb_x, aperture_ptr, g_ptr, ld_g,
@@ -1153,10 +1144,11 @@ def ssb_gather(device, tile_ptr, tile_dtype, n_frames, ld_tile, n_px, idx_ptr, n
         out_ptr, int(ld_out), stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ssb_gather')
 
 
-class SSBPlan:
+class SSBPlan(_NativePlan):
     """Owns one `ltmi_ssb_plan*`: the bright-field list (host int32 frame indices), the geometry (`ssb_geometry`), the
     cutoff, a batched 2D R2C hipFFT over the (nav_y, nav_x) scan for min(max_batch, P) bright-field pixels per
     execution and its workspace."""
+    _destroy, _last_kernel = 'ltmi_ssb_plan_destroy', 'ltmi_ssb_plan_last_kernel'
 
     def __init__(self, device, nav_y, nav_x, sig_w, idx, max_batch, geom, cutoff):
         idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
@@ -1182,18 +1174,7 @@ class SSBPlan:
     def last_kernel(self):
         """'k_transpose<4> + hipfft_r2c + k_transpose<8> + k_ssb_trotter batch=N' after the first `reconstruct` call,
         '' before"""
-        return lib().ltmi_ssb_plan_last_kernel(self._ptr).decode()
-
-    def close(self):
-        if self._ptr is not None and self._ptr.value:
-            lib().ltmi_ssb_plan_destroy(self._ptr)
-            self._ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().last_kernel()
 
 
 def ssb_trotter(device, spec_ptr, ld_spec, nav_y, nav_x, idx_ptr, n_idx, sig_w, geom, cutoff, fourier_ptr,

@@ -144,3 +144,60 @@ def test_error_codes():
     # nothing of that reached the results, and the plan still works
     got = call.run(3, 1)
     cr.compare(got, cr.reference(frames, template, peaks, 3, 1), frames, template, 1)
+
+
+# ---- one plan, two streams; plans that go away --------------------------------------------------------------------------
+STREAM_SIG = (24, 20)        # 5 frames in batches of 2: the partial last batch puts the zero-tail memset on the stream
+
+
+def test_one_plan_on_two_streams():
+    """One plan called on the default stream, on a second stream and on the default stream again, different frames each
+    time, one synchronisation at the end (tests/plan_checks.py): both transforms, the conversion, the multiply, the
+    memset of the tail and the peak kernel follow the stream of their call.  Every result is byte for byte what a fresh
+    plan of the same arguments gives for the same frames on the default stream."""
+    from libertem_amd import hip
+    import plan_checks
+    h, w = STREAM_SIG
+    peaks = cr.border_peaks(STREAM_SIG)
+    k = len(peaks)
+    template = cr.disk_template(STREAM_SIG)
+    sets = [cr.make_frames(STREAM_SIG, peaks, 4, 5, seed=40 + i, dtype='uint16')[0] for i in range(3)]
+    tiles = [torch.from_numpy(s.view(np.int16).reshape(5, h * w)).cuda() for s in sets]
+    dev_peaks = torch.from_numpy(peaks.reshape(-1).copy()).cuda()
+
+    def buffers():
+        return [torch.full((5, 2 * k), -7, dtype=torch.int32, device='cuda')] + \
+               [torch.full((5, n), np.nan, dtype=torch.float32, device='cuda') for n in (2 * k, k, k)]
+
+    def run(plan, tile, out, stream):
+        plan.correlate_peaks(tile.data_ptr(), np.uint16, 5, h * w, dev_peaks.data_ptr(), k, 4, 1,
+                             *[o.data_ptr() for o in out], stream=stream)
+
+    outs = [buffers() for _ in range(3)]
+    plan = hip.CorrPlan(0, h, w, 2, template)
+    plan_checks.three_calls_on_two_streams(lambda i, stream: run(plan, tiles[i], outs[i], stream))
+    plan.close()
+    for i in range(3):
+        fresh = hip.CorrPlan(0, h, w, 2, template)
+        ref = buffers()
+        run(fresh, tiles[i], ref, None)
+        torch.cuda.synchronize()
+        fresh.close()
+        for name, got, want in zip(NAMES, outs[i], ref):
+            assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes(), (i, name)
+        assert np.all(np.isfinite(ref[2].cpu().numpy()))
+
+
+CORR_PLAN_BYTES = 33554432
+
+
+def test_plans_go_away_completely():
+    """64 plans made and closed in a row; free memory after cycle 64 less than ONE live plan below that after cycle 8
+    (tests/plan_checks.py).  CORR_PLAN_BYTES = 33554432 bytes: torch.cuda.mem_get_info() before minus after one
+    `hip.CorrPlan(0, 24, 20, 2, template)` on the MI355X, measured at the commit before `ltmi::FftHandle` (the
+    plans then destroyed their hipFFT handles by hand); a second and a third plan made beside live ones cost the same."""
+    from libertem_amd import hip
+    import plan_checks
+    template = cr.disk_template(STREAM_SIG)
+    plan_checks.assert_plans_go_away(lambda: hip.CorrPlan(0, STREAM_SIG[0], STREAM_SIG[1], 2, template),
+                                     CORR_PLAN_BYTES, 'CorrPlan')

@@ -402,6 +402,19 @@ def test_one_plan_on_two_streams(hip, plans):
         assert np.all(np.abs(got - ref) <= F32_TOL * np.abs(ref).max()), (got, ref)
 
 
+FFT_PLAN_BYTES = 16777216
+
+
+def test_plans_go_away_completely(hip):
+    """64 plans made and closed in a row; free memory after cycle 64 less than ONE live plan below that after cycle 8
+    (tests/plan_checks.py).  FFT_PLAN_BYTES = 16777216 bytes: torch.cuda.mem_get_info() before minus after one
+    `hip.FFTPlan(0, 40, 48, 8)` on the MI355X, measured at the commit before `ltmi::FftHandle` (the
+    plans then destroyed their hipFFT handles by hand); a second and a third plan made beside live ones cost the same.
+    (40 x 48 is off the fused path: the plan holds its hipFFT handle and both workspaces from the start.)"""
+    import plan_checks
+    plan_checks.assert_plans_go_away(lambda: hip.FFTPlan(0, 40, 48, 8), FFT_PLAN_BYTES, 'FFTPlan')
+
+
 # --- 2f: the switch -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('sig', [128, 256])
 def test_switch_keeps_fused_shapes_on_hipfft(hip, sig):

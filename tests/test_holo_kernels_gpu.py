@@ -246,3 +246,55 @@ def test_error_codes():
     assert rc == -1
     # nothing of that reached the result, and the plan still works
     call.compare(call.run(), what='after the errors')
+    # ... and the creates that failed left nothing that keeps a new plan from working
+    after = Call(case, frames, 2)
+    after.compare(after.run(), what='a plan made after the errors')
+
+
+# ---- one plan, two streams; plans that go away --------------------------------------------------------------------------
+SMALLEST = min(hr.CASES, key=lambda c: c[0][0] * c[0][1])
+
+
+def test_one_plan_on_two_streams():
+    """One plan called on the default stream, on a second stream and on the default stream again, different frames each
+    time, one synchronisation at the end (tests/plan_checks.py); the smallest case, 5 frames in batches of 2, so the
+    memset of the tail runs too.  Every result is byte for byte what a fresh plan of the same arguments gives for the
+    same frames on the default stream."""
+    from libertem_amd import hip
+    import plan_checks
+    (h, w), (oh, ow), (sy, sx) = SMALLEST
+    aperture = hr.aperture_for(SMALLEST)
+    sets = [hr.noise_frames((h, w), 5, 'uint16', seed=60 + i) for i in range(3)]
+    tiles = [torch.from_numpy(s.view(np.int16).reshape(5, h * w)).cuda() for s in sets]
+
+    def run(plan, tile, out, stream):
+        plan.reconstruct(tile.data_ptr(), np.uint16, 5, h * w, out.data_ptr(), oh * ow, stream=stream)
+
+    outs = [torch.full((5, oh * ow), np.nan, dtype=torch.complex64, device='cuda') for _ in range(3)]
+    plan = hip.HoloPlan(0, h, w, oh, ow, 2, sy, sx, aperture)
+    plan_checks.three_calls_on_two_streams(lambda i, stream: run(plan, tiles[i], outs[i], stream))
+    plan.close()
+    for i in range(3):
+        fresh = hip.HoloPlan(0, h, w, oh, ow, 2, sy, sx, aperture)
+        ref = torch.full((5, oh * ow), np.nan, dtype=torch.complex64, device='cuda')
+        run(fresh, tiles[i], ref, None)
+        torch.cuda.synchronize()
+        fresh.close()
+        assert outs[i].cpu().numpy().tobytes() == ref.cpu().numpy().tobytes(), i
+        assert np.all(np.isfinite(ref.cpu().numpy()))
+
+
+HOLO_PLAN_BYTES = 25165824
+
+
+def test_plans_go_away_completely():
+    """64 plans made and closed in a row; free memory after cycle 64 less than ONE live plan below that after cycle 8
+    (tests/plan_checks.py).  HOLO_PLAN_BYTES = 25165824 bytes: torch.cuda.mem_get_info() before minus after one
+    hip.HoloPlan of SMALLEST with max_batch 2 on the MI355X, measured at the commit before `ltmi::FftHandle` (the
+    plans then destroyed their hipFFT handles by hand); a second and a third plan made beside live ones cost the same."""
+    from libertem_amd import hip
+    import plan_checks
+    (h, w), (oh, ow), (sy, sx) = SMALLEST
+    aperture = hr.aperture_for(SMALLEST)
+    plan_checks.assert_plans_go_away(lambda: hip.HoloPlan(0, h, w, oh, ow, 2, sy, sx, aperture), HOLO_PLAN_BYTES,
+                                     'HoloPlan')

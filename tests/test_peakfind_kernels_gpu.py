@@ -264,3 +264,41 @@ def test_plan_nonfinite_frames_and_errors():
         call.find(p, n_found_ptr=None)
     none = PlanCall(frames[:0], tmpl, p['num_peaks'], 2)
     assert none.find(p)['centers'].shape == (0, p['num_peaks'], 2) and none.plan.last_kernel() == ''
+
+
+def test_find_peaks_one_plan_on_two_streams():
+    """`CorrPlan.find_peaks` of one plan on the default stream, on a second stream and on the default stream again,
+    different frames each time, one synchronisation at the end (tests/plan_checks.py); 24 x 20 frames, 5 of them in
+    batches of 2, so the memset of the tail runs too.  Every result is byte for byte what a fresh plan of the same
+    arguments gives for the same frames on the default stream."""
+    from libertem_amd import hip
+    import plan_checks
+    h, w = sig = (24, 20)
+    tmpl = pr.template(sig)
+    sets = [pr.make_frames(sig, 5, 50 + i, dtype='uint16')[0] for i in range(3)]
+    p = pr.params(6, 2, threshold_abs=pr.threshold_for(sets[0], tmpl))
+    k = p['num_peaks']
+    tiles = [torch.from_numpy(s.view(np.int16).reshape(5, h * w)).cuda() for s in sets]
+
+    def buffers():
+        return [torch.full((5, n), -7, dtype=torch.int32, device='cuda') for n in (1, 2 * k)] + \
+               [torch.full((5, n), np.inf, dtype=torch.float32, device='cuda') for n in (2 * k, k, k)]
+
+    def run(plan, tile, out, stream):
+        plan.find_peaks(tile.data_ptr(), np.uint16, 5, h * w, p['num_peaks'], p['min_distance'], p['border'],
+                        p['threshold_abs'], p['threshold_rel'], p['refine_radius'], *[o.data_ptr() for o in out],
+                        stream=stream)
+
+    outs = [buffers() for _ in range(3)]
+    plan = hip.CorrPlan(0, h, w, 2, tmpl)
+    plan_checks.three_calls_on_two_streams(lambda i, stream: run(plan, tiles[i], outs[i], stream))
+    plan.close()
+    for i in range(3):
+        fresh = hip.CorrPlan(0, h, w, 2, tmpl)
+        ref = buffers()
+        run(fresh, tiles[i], ref, None)
+        torch.cuda.synchronize()
+        fresh.close()
+        for name, got, want in zip(NAMES, outs[i], ref):
+            assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes(), (i, name)
+        assert np.all(ref[0].cpu().numpy() >= 1)                 # (something was found in every frame)

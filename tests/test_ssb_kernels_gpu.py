@@ -346,3 +346,55 @@ def test_reconstruct_error_codes(generic):
     torch.cuda.synchronize()
     sr.assert_fourier(out.cpu().numpy(), ref, 'after the errors')
     plan.close()
+    # ... and the creates that failed left nothing that keeps a new plan from working
+    after = hip.SSBPlan(0, 12, 10, 28, idx, 50, geom, 4)
+    out.zero_()
+    after.reconstruct(bf.data_ptr(), 167, out.data_ptr())
+    torch.cuda.synchronize()
+    sr.assert_fourier(out.cpu().numpy(), ref, 'a plan made after the errors')
+    after.close()
+
+
+def test_one_plan_on_two_streams(generic):
+    """One plan called on the default stream, on a second stream and on the default stream again, different scans each
+    time, one synchronisation at the end (tests/plan_checks.py); the generic fixture's 167 pixels in batches of 50, so
+    the sums of a Q wait in the accumulator between the batches.  Every result is byte for byte what a fresh plan of the
+    same arguments gives for the same scan on the default stream."""
+    from libertem_amd import hip
+    import plan_checks
+    bf_host, idx, _ = generic
+    rng = np.random.default_rng(70)
+    sets = [bf_host] + [rng.poisson(40., bf_host.shape).astype(np.float32) for _ in range(2)]
+    bfs = [torch.from_numpy(s).cuda() for s in sets]
+    geom = generic_geom()
+
+    def run(plan, bf, out, stream):
+        plan.reconstruct(bf.data_ptr(), 167, out.data_ptr(), stream=stream)
+
+    outs = [torch.full((12, 10), np.nan, dtype=torch.complex64, device='cuda') for _ in range(3)]
+    plan = hip.SSBPlan(0, 12, 10, 28, idx, 50, geom, 4)
+    plan_checks.three_calls_on_two_streams(lambda i, stream: run(plan, bfs[i], outs[i], stream))
+    plan.close()
+    for i in range(3):
+        fresh = hip.SSBPlan(0, 12, 10, 28, idx, 50, geom, 4)
+        ref = torch.full((12, 10), np.nan, dtype=torch.complex64, device='cuda')
+        run(fresh, bfs[i], ref, None)
+        torch.cuda.synchronize()
+        fresh.close()
+        assert outs[i].cpu().numpy().tobytes() == ref.cpu().numpy().tobytes(), i
+        assert np.all(np.isfinite(ref.cpu().numpy()))
+
+
+SSB_PLAN_BYTES = 16777216
+
+
+def test_plans_go_away_completely(generic):
+    """64 plans made and closed in a row; free memory after cycle 64 less than ONE live plan below that after cycle 8
+    (tests/plan_checks.py).  SSB_PLAN_BYTES = 16777216 bytes: torch.cuda.mem_get_info() before minus after one
+    `hip.SSBPlan(0, 12, 10, 28, idx, 50, geom, 4)` on the MI355X, measured at the commit before `ltmi::FftHandle` (the
+    plans then destroyed their hipFFT handles by hand); a second and a third plan made beside live ones cost the same."""
+    from libertem_amd import hip
+    import plan_checks
+    _, idx, _ = generic
+    geom = generic_geom()
+    plan_checks.assert_plans_go_away(lambda: hip.SSBPlan(0, 12, 10, 28, idx, 50, geom, 4), SSB_PLAN_BYTES, 'SSBPlan')
