@@ -628,6 +628,46 @@ int ltmi_correlate_find(ltmi_corr_plan *p, const void *tile, int tile_dtype, int
                         int refine_radius, int32_t *n_found, int32_t *centers, float *refineds, float *peak_values,
                         float *peak_elevations, void *stream);
 
+/* ---- electron counting (csrc/ltmi_count.hip) --------------------------------
+ * What an event is.  For every frame of (h, w) pixels, row-major pixel number p = y w + x, with the float32
+ * thresholds t_bg (background) and t_x (x-ray; +inf switches it off):
+ *   1. v[p] = float32(pixel[p]), rounded to nearest even like ndarray.astype(float32); with `dark`, v = v - dark[p],
+ *      one float32 subtraction; with `gain`, v = v * gain[p], one float32 multiplication; subtract, then multiply;
+ *   2. u[p] = v[p] if v[p] <= t_x, else 0: an x-ray hit is zeroed and does not count, NaN compares false and becomes
+ *      0, +Inf with t_x = +inf stays and can be an event;
+ *   3. p is an EVENT iff u[p] > t_bg and, over its up to 8 neighbours q inside the frame, u[p] > u[q] where q < p and
+ *      u[p] >= u[q] where q > p: of equal neighbours the first in row-major order wins, no two events are adjacent;
+ *   4. the events of a frame are listed by ascending p; an event's value is uint8(1) or u[p] as float32.
+ * Every decision is an exact float32 comparison: the results are the bytes of the definition, and they repeat.
+ * tile: DEVICE, frame f at tile + f * ld_tile pixels (rows contiguous, ld_tile >= h w), tile_dtype one of LTMI_U8,
+ * LTMI_I8, LTMI_U16, LTMI_I16, LTMI_U32, LTMI_I32, LTMI_F32 (anything else: LTMI_E_DTYPE).  dark, gain: DEVICE
+ * float32 (h w), or NULL.  Limits: h, w >= 1, h w <= 2^31 - 1, and w <= 4096 -- a strip of rows and its two halo
+ * rows are staged in 48 KiB of LDS, which three rows of 4096 + 8 float32 fill.  n_frames < 0, a size outside the
+ * limits, ld_tile < h w, a NaN threshold: LTMI_E_SHAPE; a null tile or output with work to do: LTMI_E_INVALID.
+ * n_frames == 0 launches nothing.  Nothing is read back and the stream is not drained.
+ *
+ * n_events[f] = number of events of frame f (device int32, n_frames). */
+int ltmi_count_events(int device, const void *tile, int tile_dtype, int64_t n_frames, int h, int w, int64_t ld_tile,
+                      const float *dark, const float *gain, float t_bg, float t_x, int32_t *n_events, void *stream);
+/* Writes frame f's events to indices_out[indptr[f] - base .. indptr[f + 1] - base), ascending, and their values to
+ * the same places of values_out (values_dtype LTMI_U8: 1; LTMI_F32: u[p]; anything else: LTMI_E_DTYPE; values_out
+ * NULL: indices only).  indptr: DEVICE int64 (n_frames + 1); indices_out, values_out: DEVICE, `capacity` elements
+ * (capacity < 0: LTMI_E_SHAPE); status: DEVICE int32 (1), zeroed by the caller.  Writes go only to
+ * [indptr[f] - base, indptr[f + 1] - base) intersected with [0, capacity).  *status becomes non-zero (an atomic or)
+ * if the events of a frame do not number exactly indptr[f + 1] - indptr[f] or a range leaves [0, capacity); what
+ * then stands inside the ranges is unspecified, nothing outside them is touched.  The order of the output needs no
+ * sort and no atomic: a call's results repeat bit for bit. */
+int ltmi_store_events(int device, const void *tile, int tile_dtype, int64_t n_frames, int h, int w, int64_t ld_tile,
+                      const float *dark, const float *gain, float t_bg, float t_x, const int64_t *indptr,
+                      int64_t base, int64_t capacity, int32_t *indices_out, void *values_out, int values_dtype,
+                      int32_t *status, void *stream);
+/* Rows of a strip for frames of (h, w): min(30, h, what fits the LDS budget); 0 for sizes outside the limits.  A
+ * frame is walked in strips of this many rows (the last may be shorter). */
+int ltmi_count_strip_rows(int h, int w);
+/* "k_count_events" / "k_store_events" after the calling thread's last launching call, with " vec" where the pixels
+ * were loaded 16 bytes per lane (w a multiple of 4); "" before the first. */
+const char *ltmi_count_last_kernel(void);
+
 /* ---- off-axis hologram reconstruction (hipFFT) -----------------------------
  * With s(i, n) = i for i <= (n-1)/2, else i - n (the signed frequency of index i, fftfreq order), for every frame:
  *   F = fft2((float)tile[f]) / (sig_h sig_w)

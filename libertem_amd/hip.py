@@ -58,6 +58,7 @@ EXPORTS = (
     'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
     'ltmi_lattice_fit', 'ltmi_lattice_last_kernel',
     'ltmi_find_peaks_maps', 'ltmi_find_peaks_last_kernel', 'ltmi_correlate_find',
+    'ltmi_count_events', 'ltmi_store_events', 'ltmi_count_strip_rows', 'ltmi_count_last_kernel',
     'ltmi_holo_plan_create', 'ltmi_holo_plan_destroy', 'ltmi_holo_reconstruct', 'ltmi_holo_plan_last_kernel',
     'ltmi_holo_crop',
     'ltmi_ssb_gather', 'ltmi_ssb_plan_create', 'ltmi_ssb_plan_destroy', 'ltmi_ssb_reconstruct',
@@ -352,6 +353,12 @@ def lib():
         L.ltmi_find_peaks_last_kernel.restype = c.c_char_p
         L.ltmi_correlate_find.argtypes = [vp, vp, i32, i64, i64, i32, i32, i32, c.c_float, c.c_float, i32,
                                           vp, vp, vp, vp, vp, vp]
+        L.ltmi_count_events.argtypes = [i32, vp, i32, i64, i32, i32, i64, vp, vp, c.c_float, c.c_float, vp, vp]
+        L.ltmi_store_events.argtypes = [i32, vp, i32, i64, i32, i32, i64, vp, vp, c.c_float, c.c_float, vp, i64, i64,
+                                        vp, vp, i32, vp, vp]
+        L.ltmi_count_strip_rows.argtypes = [i32, i32]
+        L.ltmi_count_last_kernel.argtypes = []
+        L.ltmi_count_last_kernel.restype = c.c_char_p
         L.ltmi_holo_plan_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, c.POINTER(vp)]
         L.ltmi_holo_plan_destroy.argtypes = [vp]
         L.ltmi_holo_reconstruct.argtypes = [vp, vp, i32, i64, i64, vp, i64, vp]
@@ -1072,6 +1079,44 @@ def find_peaks_last_kernel():
     """'k_pf_cells + k_pf_verify + k_pf_select + k_corr_found' after the first launching `find_peaks_maps` call
     on this thread, '' before"""
     return lib().ltmi_find_peaks_last_kernel().decode()
+
+
+#: frame dtypes ltmi_count_events / ltmi_store_events take
+COUNT_DTYPES = frozenset(np.dtype(t) for t in ('u1', 'i1', 'u2', 'i2', 'u4', 'i4', 'f4'))
+#: widest frame they take (csrc/ltmi_count.hip)
+COUNT_MAX_WIDTH = 4096
+
+
+def count_events(device, tile_ptr, tile_dtype, n_frames, h, w, ld_tile, dark_ptr, gain_ptr, t_bg, t_x, n_events_ptr,
+                 stream=None):
+    """n_events[f] = number of electron events of frame f (the definition: include/ltmi.h); `dark_ptr` / `gain_ptr`:
+    device float32 (h, w) or None"""
+    check(lib().ltmi_count_events(
+        int(device), tile_ptr, dtype_code(tile_dtype), int(n_frames), int(h), int(w), int(ld_tile), dark_ptr or None,
+        gain_ptr or None, float(t_bg), float(t_x), n_events_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_count_events')
+
+
+def store_events(device, tile_ptr, tile_dtype, n_frames, h, w, ld_tile, dark_ptr, gain_ptr, t_bg, t_x, indptr_ptr,
+                 base, capacity, indices_ptr, values_ptr, values_dtype, status_ptr, stream=None):
+    """frame f's events to indices[indptr[f] - base .. indptr[f + 1] - base), ascending, their values (uint8 1 or
+    float32 u[p]) to the same places of `values_ptr` (None: indices only); `status_ptr`: device int32, non-zero
+    afterwards if `indptr` does not fit the events or the `capacity` elements"""
+    check(lib().ltmi_store_events(
+        int(device), tile_ptr, dtype_code(tile_dtype), int(n_frames), int(h), int(w), int(ld_tile), dark_ptr or None,
+        gain_ptr or None, float(t_bg), float(t_x), indptr_ptr, int(base), int(capacity), indices_ptr,
+        values_ptr or None, dtype_code(values_dtype), status_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_store_events')
+
+
+def count_strip_rows(h, w):
+    """rows of a strip of the counting kernels for frames of (h, w); 0 outside their limits"""
+    return int(lib().ltmi_count_strip_rows(int(h), int(w)))
+
+
+def count_last_kernel():
+    """'k_count_events' / 'k_store_events' (+ ' vec': 16-byte pixel loads) after this thread's last launching call"""
+    return lib().ltmi_count_last_kernel().decode()
 
 
 class HoloPlan(_NativePlan):

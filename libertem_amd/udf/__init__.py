@@ -10,6 +10,7 @@ from .correlation import CorrelationUDF, run_correlation
 from .peakfind import PeakFindUDF, run_peakfind, find_peaks, find_in_maps
 from .holography import HoloReconstructUDF, run_holo
 from .ssb import SSBUDF, run_ssb
+from .counting import EventCountUDF, EventStoreUDF, count_events, count_frames, estimate_thresholds
 from .lattice import LatticeRefineUDF, run_refine, fit_lattice, lattice_peaks, lattice_strain
 
 __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPostprocessMixin', 'UDFPreprocessMixin',
@@ -17,4 +18,5 @@ __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPost
            'RecordUDF', 'CorrelationUDF', 'run_correlation', 'PeakFindUDF', 'run_peakfind', 'find_peaks', 'find_in_maps',
            'LatticeRefineUDF', 'run_refine', 'fit_lattice',
            'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb',
+           'EventCountUDF', 'EventStoreUDF', 'count_events', 'count_frames', 'estimate_thresholds',
            'UDFRunCancelled', 'UDFException']

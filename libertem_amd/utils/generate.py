@@ -1,7 +1,8 @@
 """Synthetic test frames, under the reference's names (`libertem.utils.generate`).
 
 `hologram_frame` simulates an off-axis electron hologram from an amplitude and a phase image (Lichte & Lehmann,
-Rep. Prog. Phys. 71 (2008) 016102): the frames `libertem_amd.udf.holography` reconstructs.
+Rep. Prog. Phys. 71 (2008) 016102): the frames `libertem_amd.udf.holography` reconstructs.  `weak_phase_scan` gives
+the frames of `libertem_amd.udf.ssb`, `electron_frames` those of `libertem_amd.udf.counting`.
 """
 import numpy as np
 
@@ -104,3 +105,55 @@ def weak_phase_scan(phi, step, semiconv_pix, counts=1000.):
             exit_wave = probe * np.roll(obj, (-ry * step, -rx * step), axis=(0, 1))
             frames[ry, rx] = np.fft.fftshift(np.abs(np.fft.fft2(exit_wave)) ** 2) * (counts / (h * w))
     return frames
+
+
+def electron_frames(n, shape, rate, seed, pedestal=20, noise=4, amplitude=40, spill=15, xrays=0):
+    """
+    Frames of a direct detector at low dose with the electron events planted at known places: what
+    `libertem_amd.udf.counting` counts.
+
+    Integer noise in [0, noise] sits on the integer `pedestal`; the dark frame is pedestal + 0.25 everywhere.  The
+    frame is cut into 4 x 4 cells (a ragged edge holds no event); a cell holds an event with probability `rate`, its
+    centre at offset 1 or 2 of the cell in each axis, so centres are at least 3 pixels apart and none touches an
+    edge.  An event adds integers in [0, spill] to the 3 x 3 pixels around its centre and `amplitude` more to the
+    centre.  `xrays` pixels per frame, in cells without an event, are set to 60000.
+
+    With the defaults, background_threshold = 10 and xray_threshold = 1000 the events counted in frames - dark are
+    exactly the planted ones: a centre is at least 39.75, any of its neighbours at most 18.75, noise at most 3.75.
+
+    -> (frames uint16 (n, h, w), dark float32 (h, w), planted): planted = (indptr int64 (n + 1,), indices int32),
+    the flat pixel numbers of the centres by frame, ascending -- what `count_frames` returns first.
+    """
+    n, (h, w) = int(n), (int(s) for s in shape)
+    ncy, ncx = h // 4, w // 4
+    if n < 0 or h < 1 or w < 1:
+        raise ValueError(f"{n} frames of shape {(h, w)}")
+    if not 0 <= rate <= 1:
+        raise ValueError(f"rate {rate} must lie in [0, 1]")
+    if pedestal + noise + spill + amplitude >= 60000:
+        raise ValueError("pedestal + noise + spill + amplitude must stay below the 60000 of an x-ray hit")
+    rng = np.random.default_rng(seed)
+    frames = pedestal + rng.integers(0, noise, (n, h, w), endpoint=True)
+    chosen = rng.random((n, ncy, ncx)) < rate
+    f, cy, cx = np.nonzero(chosen)                            # (by frame, then cell row, then cell column)
+    y = 4 * cy + rng.integers(1, 2, len(f), endpoint=True)
+    x = 4 * cx + rng.integers(1, 2, len(f), endpoint=True)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            # (the 3 x 3 neighbourhoods stay inside their cells: no pixel is named twice)
+            frames[f, y + dy, x + dx] += rng.integers(0, spill, len(f), endpoint=True)
+    frames[f, y, x] += amplitude
+    if xrays:
+        for i in range(n):
+            free = np.flatnonzero(~chosen[i].reshape(-1))
+            if len(free) < xrays:
+                raise ValueError(f"frame {i} has {len(free)} cells without an event for {xrays} x-ray hits")
+            cells = rng.choice(free, size=xrays, replace=False)
+            yy = 4 * (cells // ncx) + rng.integers(0, 3, xrays, endpoint=True)
+            xx = 4 * (cells % ncx) + rng.integers(0, 3, xrays, endpoint=True)
+            frames[i, yy, xx] = 60000
+    p = y * w + x
+    order = np.lexsort((p, f))
+    indptr = np.concatenate(([0], np.cumsum(np.bincount(f, minlength=n)))).astype(np.int64)
+    dark = np.full((h, w), pedestal + 0.25, dtype=np.float32)
+    return frames.astype(np.uint16), dark, (indptr, p[order].astype(np.int32))
