@@ -668,6 +668,55 @@ int ltmi_count_strip_rows(int h, int w);
  * were loaded 16 bytes per lane (w a multiple of 4); "" before the first. */
 const char *ltmi_count_last_kernel(void);
 
+/* ---- orientation matching in polar coordinates (csrc/ltmi_orient.hip) --------
+ * Every frame against T templates at every in-plane rotation, reduced to the n_best best templates on the device.
+ * Every float32 operation below is rounded on its own (no fused multiply-add), so everything but `norm_out` is the
+ * bytes of the definition.  For a frame of (sig_h, sig_w) pixels:
+ *   1. the sampling table gives every polar point (i, j), i < n_r, j < n_phi, four taps: pixel numbers
+ *      tap_idx[i, j, 0..3] and float32 weights tap_w[i, j, 0..3] (bilinear: libertem_amd.udf.orientation.polar_table);
+ *   2. P[i, j] = (w0 v0 + w1 v1) + (w2 v2 + w3 v3), v = float32(pixel at the tap): four float32 products, three
+ *      float32 sums, in this association.  A tap of weight 0 is not read: its v is +0;
+ *   3. template t holds the spots s in [indptr[t], indptr[t + 1]): (spot_r, spot_phi, spot_w);
+ *   4. for a rotation k < n_phi: acc = +0, then over the spots in stored order
+ *      acc = acc + spot_w[s] * P[spot_r[s], (spot_phi[s] + k) mod n_phi] (one float32 multiply, one float32 add);
+ *      c[t] = the maximum of acc over k, rot[t] = the smallest k that reaches it; an empty template: c = 0, rot = 0;
+ *   5. the templates by c descending, then t ascending: the first n_best fill template_out[f, :], rotation_out[f, :],
+ *      correlation_out[f, :]; slots from min(n_best, T) on hold -1, -1, NaN;
+ *   6. norm_out[f] = float32(sqrt(sum of float64(P[i, j])^2)), summed in float64 (a fixed order: it repeats);
+ *   7. a frame with a non-finite pixel at a tap of non-zero weight: every slot -1, -1, NaN and norm_out NaN.
+ * Frames whose P or scores overflow float32 are outside the definition.
+ * A plan owns device copies of the table and the library.  tap_idx: HOST int32 (n_r, n_phi, 4), every entry in
+ * [0, sig_h sig_w); tap_w: HOST float32 (n_r, n_phi, 4), finite; indptr: HOST int64 (n_templates + 1), from 0,
+ * ascending; spot_r, spot_phi: HOST int32 in [0, n_r) and [0, n_phi); spot_w: HOST float32, finite -- all checked here.
+ * Limits: 1 <= n_best <= 16, 1 <= n_phi <= 1024, n_r >= 1, n_r n_phi <= ltmi_orient_max_polar_words() (the polar
+ * image and the kernel's other LDS share the 160 KiB of a CU), n_templates >= 1, sig_h sig_w <= 2^31 - 1; outside
+ * them, or an entry out of range: LTMI_E_SHAPE, with the offending value in ltmi_last_error; a null pointer:
+ * LTMI_E_INVALID. */
+typedef struct ltmi_orient_plan ltmi_orient_plan;   /* opaque */
+int ltmi_orient_plan_create(int device, int sig_h, int sig_w, int n_r, int n_phi, const int32_t *tap_idx,
+                            const float *tap_w, int n_templates, const int64_t *indptr, const int32_t *spot_r,
+                            const int32_t *spot_phi, const float *spot_w, int n_best, ltmi_orient_plan **out);
+int ltmi_orient_plan_destroy(ltmi_orient_plan *p);
+/* Steps 2 - 7 for n_frames frames.  tile: DEVICE, frame f at tile + f * ld_tile pixels (rows contiguous, ld_tile >=
+ * sig_h sig_w), tile_dtype one of LTMI_U8, LTMI_I8, LTMI_U16, LTMI_I16, LTMI_U32, LTMI_I32, LTMI_F32 (anything else:
+ * LTMI_E_DTYPE).  template_out, rotation_out: DEVICE int32 (n_frames, n_best); correlation_out: DEVICE float32
+ * (n_frames, n_best); norm_out: DEVICE float32 (n_frames).  One workgroup per frame at a time; no atomics, a call's
+ * results repeat bit for bit.  n_frames < 0 or ld_tile too small: LTMI_E_SHAPE; a null pointer with work to do:
+ * LTMI_E_INVALID; n_frames == 0 launches nothing.  Nothing is read back and the stream is not drained. */
+int ltmi_orient_match(ltmi_orient_plan *p, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
+                      int32_t *template_out, int32_t *rotation_out, float *correlation_out, float *norm_out,
+                      void *stream);
+/* Step 2 alone: P of frame f to polar_out + f * ld_polar (DEVICE float32, ld_polar >= n_r n_phi, else LTMI_E_SHAPE),
+ * as computed -- non-finite taps propagate.  Arguments and errors as ltmi_orient_match. */
+int ltmi_orient_polar(ltmi_orient_plan *p, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
+                      float *polar_out, int64_t ld_polar, void *stream);
+/* "k_orient_match<dtype,NCH> grid=G lds=B" (NCH: the accumulators a lane holds, at least ceil(n_phi / 64)) or
+ * "k_orient_polar<dtype>" after the plan's last launching call, "" before.  The string lives as long as the plan. */
+const char *ltmi_orient_plan_last_kernel(const ltmi_orient_plan *p);
+/* The largest n_r n_phi a plan takes, and the number of templates whose scores are selected from at a time. */
+int ltmi_orient_max_polar_words(void);
+int ltmi_orient_score_block(void);
+
 /* ---- off-axis hologram reconstruction (hipFFT) -----------------------------
  * With s(i, n) = i for i <= (n-1)/2, else i - n (the signed frequency of index i, fftfreq order), for every frame:
  *   F = fft2((float)tile[f]) / (sig_h sig_w)

@@ -59,6 +59,8 @@ EXPORTS = (
     'ltmi_lattice_fit', 'ltmi_lattice_last_kernel',
     'ltmi_find_peaks_maps', 'ltmi_find_peaks_last_kernel', 'ltmi_correlate_find',
     'ltmi_count_events', 'ltmi_store_events', 'ltmi_count_strip_rows', 'ltmi_count_last_kernel',
+    'ltmi_orient_plan_create', 'ltmi_orient_plan_destroy', 'ltmi_orient_match', 'ltmi_orient_polar',
+    'ltmi_orient_plan_last_kernel', 'ltmi_orient_max_polar_words', 'ltmi_orient_score_block',
     'ltmi_holo_plan_create', 'ltmi_holo_plan_destroy', 'ltmi_holo_reconstruct', 'ltmi_holo_plan_last_kernel',
     'ltmi_holo_crop',
     'ltmi_ssb_gather', 'ltmi_ssb_plan_create', 'ltmi_ssb_plan_destroy', 'ltmi_ssb_reconstruct',
@@ -359,6 +361,14 @@ def lib():
         L.ltmi_count_strip_rows.argtypes = [i32, i32]
         L.ltmi_count_last_kernel.argtypes = []
         L.ltmi_count_last_kernel.restype = c.c_char_p
+        L.ltmi_orient_plan_create.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, c.POINTER(vp)]
+        L.ltmi_orient_plan_destroy.argtypes = [vp]
+        L.ltmi_orient_match.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp]
+        L.ltmi_orient_polar.argtypes = [vp, vp, i32, i64, i64, vp, i64, vp]
+        L.ltmi_orient_plan_last_kernel.argtypes = [vp]
+        L.ltmi_orient_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_orient_max_polar_words.argtypes = []
+        L.ltmi_orient_score_block.argtypes = []
         L.ltmi_holo_plan_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, c.POINTER(vp)]
         L.ltmi_holo_plan_destroy.argtypes = [vp]
         L.ltmi_holo_reconstruct.argtypes = [vp, vp, i32, i64, i64, vp, i64, vp]
@@ -1117,6 +1127,75 @@ def count_strip_rows(h, w):
 def count_last_kernel():
     """'k_count_events' / 'k_store_events' (+ ' vec': 16-byte pixel loads) after this thread's last launching call"""
     return lib().ltmi_count_last_kernel().decode()
+
+
+#: frame dtypes ltmi_orient_match / ltmi_orient_polar take
+ORIENT_DTYPES = COUNT_DTYPES
+
+
+def orient_max_polar_words():
+    """the largest n_r * n_phi an OrientPlan takes: the polar image shares the LDS of a CU with the kernel's scores"""
+    return int(lib().ltmi_orient_max_polar_words())
+
+
+def orient_score_block():
+    """templates whose scores the matching kernel selects from at a time (csrc/ltmi_orient.hip)"""
+    return int(lib().ltmi_orient_score_block())
+
+
+class OrientPlan(_NativePlan):
+    """Owns one `ltmi_orient_plan*`: the device copies of a polar sampling table (tap_idx int32, tap_w float32, both
+    (n_r, n_phi, 4)) for frames of (sig_h, sig_w) and of a template library (indptr (T + 1,), spot_r, spot_phi, spot_w),
+    and the number of result slots n_best.  Every index and range is checked by the library (include/ltmi.h)."""
+    _destroy, _last_kernel = 'ltmi_orient_plan_destroy', 'ltmi_orient_plan_last_kernel'
+
+    def __init__(self, device, sig_h, sig_w, tap_idx, tap_w, library, n_best):
+        tap_idx = np.ascontiguousarray(tap_idx, dtype=np.int32)
+        tap_w = np.ascontiguousarray(tap_w, dtype=np.float32)
+        if tap_idx.ndim != 3 or tap_idx.shape[2] != 4 or tap_w.shape != tap_idx.shape:
+            raise ValueError(f"sampling table of shapes {tap_idx.shape} and {tap_w.shape}, not two of (n_r, n_phi, 4)")
+        indptr, spot_r, spot_phi, spot_w = library
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        spot_r = np.ascontiguousarray(spot_r, dtype=np.int32)
+        spot_phi = np.ascontiguousarray(spot_phi, dtype=np.int32)
+        spot_w = np.ascontiguousarray(spot_w, dtype=np.float32)
+        if indptr.ndim != 1 or indptr.size < 1:
+            raise ValueError(f"indptr of shape {indptr.shape}, not (T + 1,)")
+        n_spots = int(indptr[-1])
+        if not (spot_r.shape == spot_phi.shape == spot_w.shape == (max(n_spots, 0),)):
+            raise ValueError(f"indptr ends at {n_spots}, the spot arrays have shapes {spot_r.shape}, {spot_phi.shape} "
+                             f"and {spot_w.shape}")
+        n_r, n_phi = tap_idx.shape[:2]
+        out = ctypes.c_void_p()
+
+        def ptr(a):
+            return a.ctypes.data_as(ctypes.c_void_p)
+
+        check(lib().ltmi_orient_plan_create(int(device), int(sig_h), int(sig_w), n_r, n_phi, ptr(tap_idx), ptr(tap_w),
+                                            indptr.size - 1, ptr(indptr), ptr(spot_r), ptr(spot_phi), ptr(spot_w),
+                                            int(n_best), ctypes.byref(out)), 'ltmi_orient_plan_create')
+        self._ptr = out
+        self.device, self.sig, self.polar_shape = int(device), (int(sig_h), int(sig_w)), (n_r, n_phi)
+        self.n_templates, self.n_best = indptr.size - 1, int(n_best)
+
+    def match(self, tile_ptr, tile_dtype, n_frames, ld_tile, template_ptr, rotation_ptr, correlation_ptr, norm_ptr,
+              stream=None):
+        """the n_best best templates of every frame: template, rotation int32 and correlation float32
+        (n_frames, n_best), polar_norm float32 (n_frames): device pointers (include/ltmi.h)"""
+        check(lib().ltmi_orient_match(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), template_ptr, rotation_ptr,
+            correlation_ptr, norm_ptr, stream if isinstance(stream, int) else _stream_ptr(stream)),
+            'ltmi_orient_match')
+
+    def polar(self, tile_ptr, tile_dtype, n_frames, ld_tile, polar_ptr, ld_polar, stream=None):
+        """the polar image of frame f, float32 (n_r * n_phi), to polar_ptr + f * ld_polar elements"""
+        check(lib().ltmi_orient_polar(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), polar_ptr, int(ld_polar),
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_orient_polar')
+
+    def last_kernel(self):
+        """'k_orient_match<dtype,NCH> grid=G lds=B' or 'k_orient_polar<dtype>' after the last launching call"""
+        return super().last_kernel()
 
 
 class HoloPlan(_NativePlan):

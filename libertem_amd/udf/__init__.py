@@ -11,6 +11,9 @@ from .peakfind import PeakFindUDF, run_peakfind, find_peaks, find_in_maps
 from .holography import HoloReconstructUDF, run_holo
 from .ssb import SSBUDF, run_ssb
 from .counting import EventCountUDF, EventStoreUDF, count_events, count_frames, estimate_thresholds
+from .orientation import (
+    OrientationMatchUDF, run_orientation_match, polar_table, polar_library, polar_frames, match_polar, rotation_angles,
+)
 from .lattice import LatticeRefineUDF, run_refine, fit_lattice, lattice_peaks, lattice_strain
 
 __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPostprocessMixin', 'UDFPreprocessMixin',
@@ -19,4 +22,5 @@ __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPost
            'LatticeRefineUDF', 'run_refine', 'fit_lattice',
            'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb',
            'EventCountUDF', 'EventStoreUDF', 'count_events', 'count_frames', 'estimate_thresholds',
-           'UDFRunCancelled', 'UDFException']
+           'OrientationMatchUDF', 'run_orientation_match', 'polar_table', 'polar_library', 'polar_frames',
+           'match_polar', 'rotation_angles', 'UDFRunCancelled', 'UDFException']

@@ -157,3 +157,36 @@ def electron_frames(n, shape, rate, seed, pedestal=20, noise=4, amplitude=40, sp
     indptr = np.concatenate(([0], np.cumsum(np.bincount(f, minlength=n)))).astype(np.int64)
     dark = np.full((h, w), pedestal + 0.25, dtype=np.float32)
     return frames.astype(np.uint16), dark, (indptr, p[order].astype(np.int32))
+
+
+def spot_pattern_frames(spot_lists, picks, shape, center, sigma=1.2, counts=1000., beam=200., background=2., seed=0):
+    """
+    Diffraction patterns of known templates at known in-plane rotations: what `libertem_amd.udf.orientation` matches.
+
+    `spot_lists` holds one (qy, qx, intensity) triple of arrays per template, positions in pixels relative to
+    `center` = (cy, cx); `picks` is a list of (template, angle in radians), one frame each.  A frame is the sum of
+    Gaussians of width `sigma`: one of height counts * intensity at every spot of the template, rotated by the angle
+    (qx' = qx cos a - qy sin a, qy' = qx sin a + qy cos a: atan2(qy, qx) grows by a), one of height `beam` at the
+    centre, on a flat `background`; every pixel is then drawn from the Poisson distribution of that mean.
+
+    -> frames uint16 (len(picks), h, w), clipped at 65535
+    """
+    h, w = (int(s) for s in shape)
+    cy, cx = (float(c) for c in center)
+    if h < 1 or w < 1:
+        raise ValueError(f"frames of shape {(h, w)}")
+    if sigma <= 0:
+        raise ValueError(f"sigma {sigma} must be positive")
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[:h, :w].astype(np.float64)
+    frames = np.empty((len(picks), h, w), dtype=np.uint16)
+    for i, (t, angle) in enumerate(picks):
+        qy, qx, intensity = (np.asarray(a, dtype=np.float64).reshape(-1) for a in spot_lists[int(t)])
+        ca, sa = np.cos(float(angle)), np.sin(float(angle))
+        py, px = cy + qx * sa + qy * ca, cx + qx * ca - qy * sa
+        mean = np.full((h, w), float(background))
+        mean += beam * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * sigma ** 2))
+        for y0, x0, a in zip(py, px, intensity):
+            mean += counts * a * np.exp(-((yy - y0) ** 2 + (xx - x0) ** 2) / (2 * sigma ** 2))
+        frames[i] = np.minimum(rng.poisson(mean), 65535).astype(np.uint16)
+    return frames
