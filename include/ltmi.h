@@ -45,7 +45,7 @@ extern "C" {
 #define LTMI_E_INVALID (-1)      /* bad argument (null pointer, negative size, ...) */
 #define LTMI_E_DTYPE (-2)        /* dtype combination not supported */
 #define LTMI_E_SHAPE (-3)        /* shapes do not match the handle */
-#define LTMI_E_NOMEM (-4)        /* host allocation failed */
+#define LTMI_E_NOMEM (-4)        /* host allocation failed; a WDD filter that does not fit the device */
 #define LTMI_E_RCCL_BASE 10000   /* a failing RCCL call returns LTMI_E_RCCL_BASE + ncclResult_t */
 
 /* dtype codes (numpy names) */
@@ -817,6 +817,59 @@ const char *ltmi_ssb_plan_last_kernel(const ltmi_ssb_plan *p);
  * LTMI_E_SHAPE. */
 int ltmi_ssb_trotter(int device, const void *spec, int64_t ld_spec, int nav_y, int nav_x, const int32_t *idx_dev,
                      int n_idx, int sig_w, const double *geom, int cutoff, void *fourier_out, void *stream);
+
+/* ---- Wigner-distribution deconvolution ptychography (hipFFT) ---------------
+ * The scan, s(i, n), d(Q), the geometry array and the float64 disk predicates are those of the single-sideband section
+ * above.  window[LTMI_WDD_WINDOW] = { y0, x0, By, Bx } (HOST ints) names the detector pixels [y0, y0 + By) x
+ * [x0, x0 + Bx); window pixel K = v Bx + u is detector pixel (y0 + v, x0 + u) -- the coordinates never address memory.
+ * P = the window pixels with (y - cy)^2 + (x - cx)^2 < semiconv_pix^2 (the caller chooses a window that holds the whole
+ * disk; the library does not test that).  For every Q = (iy, ix), the DC included:
+ *   Gamma[K] = 1 where K lies in that disk and in the one centred at (cy, cx) - d(Q), else 0
+ *   chi[rho] = sum_K Gamma[K] exp(+2 pi i (v rho_y / By + u rho_x / Bx))
+ *   W[rho]   = conj(chi[rho]) / (|chi[rho]|^2 + epsilon P^2)
+ *   F[Q, K]  = sum_rho W[rho] exp(+2 pi i (v rho_y / By + u rho_x / Bx))
+ *   S[Q]     = sum_K G[K, Q] F[Q, K] / (By Bx)
+ *   fourier[Q] = conj(S[(-iy) mod nav_y, (-ix) mod nav_x]) / |S[0, 0]|
+ * chi and F come from an unnormalised backward complex64 hipFFT, W from a float64 quotient cast once; S accumulates in
+ * float64 in a fixed order (thread, wave shuffle tree, waves in order, batches in order) and is cast to complex64 once.
+ * A Q whose two disks share no window pixel has F = 0 and S = 0 exactly.  No atomics: a call repeats bit for bit.
+ * All-zero data gives NaN (0 / 0). */
+#define LTMI_WDD_WINDOW 4
+/* F of the Qs q0 <= iy nav_x + ix < q0 + n_q -> filter_out, DEVICE complex64 (n_q, By Bx), contiguous.  q_batch Qs
+ * per hipFFT execution (k_wdd_gamma, backward C2C, k_wdd_wiener, backward C2C).  The call owns its hipFFT plan and a
+ * workspace of min(q_batch, n_q) windows and returns when the work on `stream` is done.  n_q == 0 launches nothing.
+ * A non-positive scan or one of a single position, By < 1, Bx < 1, a non-positive or non-finite epsilon, a geometry
+ * the single-sideband plan refuses, Qs outside the scan, P = 0, a batch of more than 2^31 - 1 values: LTMI_E_SHAPE; a
+ * null pointer, q_batch < 1: LTMI_E_INVALID. */
+int ltmi_wdd_filter(int device, int nav_y, int nav_x, const int *window, const double *geom, double epsilon,
+                    int64_t q0, int64_t n_q, int q_batch, void *filter_out, void *stream);
+/* acc[Q] (+)= sum over j < n_k of G[j, Q] filter[Q ld_filter + k0 + j] for every Q of the scan.  spec: DEVICE
+ * complex64 half spectra laid out as ltmi_ssb_trotter takes them, spec[(iy (nav_x/2 + 1) + ix) ld_spec + j] = G[j, iy,
+ * ix]; a Q with ix > nav_x / 2 reads the conjugate at ((nav_y - iy) mod nav_y, nav_x - ix).  acc: DEVICE float64
+ * (nav_y nav_x, 2), real and imaginary part; first != 0: the sums start at zero, else at what acc holds.  One launch of
+ * k_wdd_dot, one workgroup per Q.  A non-positive scan, k0 < 0, n_k < 1, ld_spec < n_k, ld_filter < k0 + n_k:
+ * LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID. */
+int ltmi_wdd_dot(int device, const void *spec, int64_t ld_spec, int nav_y, int nav_x, const void *filter,
+                 int64_t ld_filter, int k0, int n_k, double *acc, int first, void *stream);
+/* fourier_out[Q] (DEVICE complex64 (nav_y, nav_x)) = conj(S[-Q]) / |S[0, 0]| with S = acc / n_window: one launch of
+ * k_wdd_finish.  Errors as for ltmi_wdd_dot, and n_window < 1: LTMI_E_SHAPE. */
+int ltmi_wdd_finish(int device, const double *acc, int nav_y, int nav_x, int n_window, void *fourier_out, void *stream);
+/* A plan owns F for every Q (nav_y nav_x By Bx complex64, built at creation on the null stream), 16 bytes per Q for
+ * the sums, one batched real-to-complex hipFFT of (nav_y, nav_x), min(max_batch, By Bx) window pixels per execution,
+ * and the workspace of the single-sideband plan.  F that does not fit into the free device memory: LTMI_E_NOMEM, the
+ * text gives the bytes needed.  The other errors as for ltmi_wdd_filter and ltmi_ssb_plan_create. */
+typedef struct ltmi_wdd_plan ltmi_wdd_plan;   /* opaque */
+int ltmi_wdd_plan_create(int device, int nav_y, int nav_x, const int *window, int max_batch, const double *geom,
+                         double epsilon, ltmi_wdd_plan **out);
+int ltmi_wdd_plan_destroy(ltmi_wdd_plan *p);
+/* bf: device float32 (nav_y nav_x, By Bx), rows ld_bf elements apart (what ltmi_ssb_gather wrote for the window's
+ * index list); fourier_out: device complex64 (nav_y, nav_x), contiguous, the unshifted layout.  Per batch the front
+ * end of ltmi_ssb_reconstruct, then k_wdd_dot; k_wdd_finish after the last.  Nothing is read back and the stream is
+ * not drained.  ld_bf < By Bx: LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID. */
+int ltmi_wdd_reconstruct(ltmi_wdd_plan *p, const float *bf, int64_t ld_bf, void *fourier_out, void *stream);
+/* "k_transpose<4> + hipfft_r2c + k_transpose<8> + k_wdd_dot + k_wdd_finish batch=N" after the first
+ * ltmi_wdd_reconstruct call of this plan, "" before.  The string lives as long as the plan. */
+const char *ltmi_wdd_plan_last_kernel(const ltmi_wdd_plan *p);
 
 /* ---- lattice fit to the matched peaks -------------------------------------------------------------
  * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]

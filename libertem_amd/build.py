@@ -22,8 +22,8 @@ LIBDIR = os.path.join(HERE, '_lib')
 LIB = os.path.join(LIBDIR, 'libltmi.so')
 OBJDIR = os.path.join(HERE, '_lib', 'obj')
 
-SOURCES = ['ltmi_capi.cpp', 'ltmi_comm.cpp', 'ltmi_dense.hip', 'ltmi_sparse.hip', 'ltmi_reduce.hip', 'ltmi_fft.hip', 'ltmi_corr.hip', 'ltmi_holo.hip', 'ltmi_ssb.hip', 'ltmi_peakfind.hip', 'ltmi_lattice.hip', 'ltmi_dense64.hip', 'ltmi_bell.hip', 'ltmi_mib.hip', 'ltmi_split.hip', 'ltmi_scatter.hip', 'ltmi_labels.hip', 'ltmi_cryst.hip', 'ltmi_fold.hip', 'ltmi_guard.hip', 'ltmi_moments.hip', 'ltmi_framestats.hip', 'ltmi_csrframes.hip', 'ltmi_k2is.hip', 'ltmi_frms6.hip', 'ltmi_records.hip', 'ltmi_transpose.hip', 'ltmi_count.hip', 'ltmi_orient.hip']
-# hipFFT for the Fourier-space operators (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip).  The loader binds libhipfft.so.0 to the copy
+SOURCES = ['ltmi_capi.cpp', 'ltmi_comm.cpp', 'ltmi_dense.hip', 'ltmi_sparse.hip', 'ltmi_reduce.hip', 'ltmi_fft.hip', 'ltmi_corr.hip', 'ltmi_holo.hip', 'ltmi_ssb.hip', 'ltmi_wdd.hip', 'ltmi_peakfind.hip', 'ltmi_lattice.hip', 'ltmi_dense64.hip', 'ltmi_bell.hip', 'ltmi_mib.hip', 'ltmi_split.hip', 'ltmi_scatter.hip', 'ltmi_labels.hip', 'ltmi_cryst.hip', 'ltmi_fold.hip', 'ltmi_guard.hip', 'ltmi_moments.hip', 'ltmi_framestats.hip', 'ltmi_csrframes.hip', 'ltmi_k2is.hip', 'ltmi_frms6.hip', 'ltmi_records.hip', 'ltmi_transpose.hip', 'ltmi_count.hip', 'ltmi_orient.hip']
+# hipFFT for the Fourier-space operators (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip, ltmi_wdd.hip).  The loader binds libhipfft.so.0 to the copy
 # torch already has in the process (same soname), i.e. the one that matches torch's HIP runtime.
 LINK_LIBS = ['-L/opt/rocm/lib', '-lhipfft', '-ldl']
 ARCH = 'gfx950'
@@ -41,7 +41,7 @@ def find_hipcc():
 def _deps(src):
     deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'ltmi_common.h'), os.path.join(CSRC, 'ltmi_tiles.h'),
             os.path.join(CSRC, 'ltmi_switches.h'), os.path.join(CSRC, 'ltmi_tuning.h'),
-            os.path.join(CSRC, 'ltmi_fftshare.h'), header_path(),
+            os.path.join(CSRC, 'ltmi_fftshare.h'), os.path.join(CSRC, 'ltmi_ssbshare.h'), header_path(),
             os.path.join(CSRC, 'ltmi_scatter_loop.inc') if src == 'ltmi_scatter.hip' else '',
             os.path.abspath(__file__)]
     return [d for d in deps if os.path.exists(d)]

@@ -7,7 +7,7 @@
 // batched 2D real-to-complex hipFFT over the scan axes, ltmi_transpose2d ((batch, Ny Nxc) -> (Ny Nxc, batch)), so that
 // the workgroup of one Q reads its pixels contiguously; the partial sums of a batch wait in a per-Q accumulator.
 // No atomics: a second call gives the same bytes.
-#include "ltmi_fftshare.h"
+#include "ltmi_ssbshare.h"
 #include <algorithm>
 #include <cmath>
 
@@ -16,12 +16,6 @@
 #pragma clang fp contract(off)
 
 namespace ltmi {
-
-// the geometry of include/ltmi.h's `geom` array, plus the shapes the kernel needs
-struct SsbGeom {
-    double lamb, dy, dx, semiconv, semiconv_pix, cy, cx, t00, t01, t10, t11;
-    int ny, nx, sig_w, cutoff;
-};
 
 // what a Q has summed so far: the complex sums over pos and neg in float64, and the two pixel counts
 struct SsbAcc {
@@ -42,23 +36,6 @@ k_ssb_gather(const T *__restrict__ tile, int64_t ld, int64_t n_frames, int64_t n
     const bool inside = i >= 0 && i < n_px;
     for (int64_t f = blockIdx.y; f < n_frames; f += gridDim.y)
         out[f * ld_out + k] = inside ? (float)tile[f * ld + i] : 0.f;
-}
-
-__host__ __device__ static inline int ssb_signed(int i, int n) { return i <= (n - 1) / 2 ? i : i - n; }
-
-// d = T q lamb semiconv_pix / semiconv for Q = (iy, ix), q = (s(iy) / (Ny dy), s(ix) / (Nx dx)): the shift of the
-// diffracted disks in detector pixels, evaluated left to right
-__device__ static inline void ssb_shift(const SsbGeom &g, int iy, int ix, double *d_y, double *d_x) {
-    const double qy = (double)ssb_signed(iy, g.ny) / ((double)g.ny * g.dy);
-    const double qx = (double)ssb_signed(ix, g.nx) / ((double)g.nx * g.dx);
-    const double ty = g.t00 * qy + g.t01 * qx;
-    const double tx = g.t10 * qy + g.t11 * qx;
-    *d_y = ty * g.lamb * g.semiconv_pix / g.semiconv;
-    *d_x = tx * g.lamb * g.semiconv_pix / g.semiconv;
-}
-
-__device__ static inline bool ssb_in_disk(double y, double x, double cy, double cx, double r2) {
-    return (y - cy) * (y - cy) + (x - cx) * (x - cx) < r2;
 }
 
 // One workgroup per Q = (iy, ix), walking the Qs with a grid stride.  Thread t takes the pixels t, t + 256, ... of
@@ -177,9 +154,8 @@ static int ssb_trotter_launch(const hipfftComplex *spec, int64_t ld_spec, const 
     return LTMI_OK;
 }
 
-// what the plan and ltmi_ssb_trotter ask of the shapes and of the geometry; fills `g`
-static int ssb_check(const char *who, int ny, int nx, int n_idx, int sig_w, const double *geom, int cutoff,
-                     SsbGeom *g) {
+// what the plans and the single-step entry points ask of the shapes and of the geometry; fills `g`
+int ssb_check(const char *who, int ny, int nx, int n_idx, int sig_w, const double *geom, int cutoff, SsbGeom *g) {
     if (ny <= 0 || nx <= 0) LTMI_FAIL(LTMI_E_SHAPE, "%s: scan %d x %d must be positive", who, ny, nx);
     if ((int64_t)ny * nx < 2)
         LTMI_FAIL(LTMI_E_SHAPE, "%s: a scan of one position has no spatial frequency to reconstruct", who);
@@ -196,6 +172,29 @@ static int ssb_check(const char *who, int ny, int nx, int n_idx, int sig_w, cons
     return LTMI_OK;
 }
 
+int SsbFront::setup(const char *who, const SsbGeom &g, int batch_) {
+    const int64_t n_nav = (int64_t)g.ny * g.nx;
+    const int n_spec = g.ny * (g.nx / 2 + 1);
+    batch = batch_;
+    hipError_t e = real_buf.alloc_zero((size_t)batch * n_nav);
+    if (e == hipSuccess) e = spec.alloc_zero((size_t)batch * n_spec);
+    if (e == hipSuccess) e = spec_t.alloc_zero((size_t)batch * n_spec);
+    if (e != hipSuccess) LTMI_FAIL((int)e, "%s: workspace allocation failed: %s", who, hipGetErrorString(e));
+    int n[2] = {g.ny, g.nx};                    // a line scan is a batch of 1D transforms
+    return g.ny == 1 ? fwd.plan_many(1, n + 1, (int)n_nav, n_spec, HIPFFT_R2C, batch)
+                     : fwd.plan_many(2, n, (int)n_nav, n_spec, HIPFFT_R2C, batch);
+}
+
+int SsbFront::run(int device, const SsbGeom &g, const float *bf, int64_t ld_bf, int64_t k0, int64_t n, void *stream) {
+    const int64_t n_nav = (int64_t)g.ny * g.nx;
+    const int64_t n_spec = (int64_t)g.ny * (g.nx / 2 + 1);
+    // column k of bf = the scan image of pixel k
+    int rc = ltmi_transpose2d(device, bf + k0, ld_bf, n_nav, n, 4, real_buf, n_nav, stream);
+    if (rc == LTMI_OK) rc = fwd.r2c(real_buf, spec);
+    if (rc == LTMI_OK) rc = ltmi_transpose2d(device, spec, n_spec, n, n_spec, 8, spec_t, batch, stream);
+    return rc;
+}
+
 }  // namespace ltmi
 
 using namespace ltmi;
@@ -206,26 +205,16 @@ struct ltmi_ssb_plan {
     int batch = 0;                      // bright-field pixels per hipFFT execution
     SsbGeom g = {};
     DevBuf<int32_t> idx;                // (P): the bright-field list
-    DevBuf<float> real_buf;             // (batch, ny, nx) f32: one scan image per bright-field pixel
-    DevBuf<hipfftComplex> spec;         // (batch, ny, nxc) c64
-    DevBuf<hipfftComplex> spec_t;       // (ny nxc, batch) c64: the same, a Q's pixels contiguous
+    SsbFront front;                     // bf columns -> spectra (ny nxc, batch), and its workspace
     DevBuf<SsbAcc> acc;                 // (ny nx): the sums of the batches so far (plans of more than one batch)
-    FftHandle fwd;                      // batched R2C over the scan axes
     char last_kernel[128] = {0};
 };
 
 static int ssb_setup(ltmi_ssb_plan *p, const int32_t *idx_host) {
-    const int64_t n_nav = (int64_t)p->g.ny * p->g.nx;
-    const int n_spec = p->g.ny * (p->g.nx / 2 + 1);
     hipError_t e = p->idx.upload(idx_host, (size_t)p->n_idx);
-    if (e == hipSuccess) e = p->real_buf.alloc_zero((size_t)p->batch * n_nav);
-    if (e == hipSuccess) e = p->spec.alloc_zero((size_t)p->batch * n_spec);
-    if (e == hipSuccess) e = p->spec_t.alloc_zero((size_t)p->batch * n_spec);
-    if (e == hipSuccess && p->batch < p->n_idx) e = p->acc.alloc_zero((size_t)n_nav);
+    if (e == hipSuccess && p->batch < p->n_idx) e = p->acc.alloc_zero((size_t)p->g.ny * p->g.nx);
     if (e != hipSuccess) LTMI_FAIL((int)e, "ltmi_ssb_plan_create: workspace allocation failed: %s", hipGetErrorString(e));
-    int n[2] = {p->g.ny, p->g.nx};              // a line scan is a batch of 1D transforms
-    return p->g.ny == 1 ? p->fwd.plan_many(1, n + 1, (int)n_nav, n_spec, HIPFFT_R2C, p->batch)
-                        : p->fwd.plan_many(2, n, (int)n_nav, n_spec, HIPFFT_R2C, p->batch);
+    return p->front.setup("ltmi_ssb_plan_create", p->g, p->batch);
 }
 
 extern "C" int ltmi_ssb_gather(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
@@ -253,15 +242,7 @@ extern "C" int ltmi_ssb_plan_create(int device, int nav_y, int nav_x, int sig_w,
     SsbGeom g;
     const int rc_shape = ssb_check("ltmi_ssb_plan_create", nav_y, nav_x, n_idx, sig_w, geom, cutoff, &g);
     if (rc_shape != LTMI_OK) return rc_shape;
-    if (nav_x == 1) {
-        // a scan of one column is a scan of one row with the roles of the axes exchanged: the same scan images, the
-        // same Qs in the same order, and T q = (t00 qy + 0, t10 qy + 0) either way, bit for bit
-        g.nx = nav_y;
-        g.ny = 1;
-        std::swap(g.dy, g.dx);
-        std::swap(g.t00, g.t01);
-        std::swap(g.t10, g.t11);
-    }
+    ssb_column_as_row(&g);
     const int batch = std::min(max_batch, n_idx);
     if ((int64_t)batch * nav_y * nav_x > INT32_MAX)
         LTMI_FAIL(LTMI_E_SHAPE, "ltmi_ssb_plan_create: a batch of %d scans of %d x %d exceeds 2^31 - 1 values", batch,
@@ -287,22 +268,16 @@ extern "C" int ltmi_ssb_reconstruct(ltmi_ssb_plan *p, const float *bf, int64_t l
     if (!bf || !fourier_out) LTMI_FAIL(LTMI_E_INVALID, "ltmi_ssb_reconstruct: null pointer");
     LTMI_HIP(hipSetDevice(p->device));
     hipStream_t stream = (hipStream_t)stream_;
-    const int rc_bind = p->fwd.bind(stream);
+    const int rc_bind = p->front.fwd.bind(stream);
     if (rc_bind != LTMI_OK) return rc_bind;
     snprintf(p->last_kernel, sizeof(p->last_kernel), "k_transpose<4> + hipfft_r2c + k_transpose<8> + k_ssb_trotter batch=%d",
              p->batch);
-    const int64_t n_nav = (int64_t)p->g.ny * p->g.nx;
-    const int64_t n_spec = (int64_t)p->g.ny * (p->g.nx / 2 + 1);
     // the batches are bright-field pixels here
     return for_each_batch(p->n_idx, p->batch, [&](int64_t k0, int64_t n) {
-        // column k of bf = the scan image of bright-field pixel k; the plan always transforms `batch` images: a
-        // partial last batch leaves the images of an earlier one in the tail, whose spectra are never read
-        int rc = ltmi_transpose2d(p->device, bf + k0, ld_bf, n_nav, n, 4, p->real_buf, n_nav, stream_);
-        if (rc == LTMI_OK) rc = p->fwd.r2c(p->real_buf, p->spec);
-        if (rc == LTMI_OK) rc = ltmi_transpose2d(p->device, p->spec, n_spec, n, n_spec, 8, p->spec_t, p->batch, stream_);
+        const int rc = p->front.run(p->device, p->g, bf, ld_bf, k0, n, stream_);
         if (rc != LTMI_OK) return rc;
-        return ssb_trotter_launch(p->spec_t, p->batch, p->idx + k0, (int)n, p->g, p->acc, k0 == 0, k0 + n == p->n_idx,
-                                  (hipfftComplex *)fourier_out, stream);
+        return ssb_trotter_launch(p->front.spec_t, p->batch, p->idx + k0, (int)n, p->g, p->acc, k0 == 0,
+                                  k0 + n == p->n_idx, (hipfftComplex *)fourier_out, stream);
     });
 }
 

@@ -65,6 +65,8 @@ EXPORTS = (
     'ltmi_holo_crop',
     'ltmi_ssb_gather', 'ltmi_ssb_plan_create', 'ltmi_ssb_plan_destroy', 'ltmi_ssb_reconstruct',
     'ltmi_ssb_plan_last_kernel', 'ltmi_ssb_trotter',
+    'ltmi_wdd_filter', 'ltmi_wdd_dot', 'ltmi_wdd_finish', 'ltmi_wdd_plan_create', 'ltmi_wdd_plan_destroy',
+    'ltmi_wdd_reconstruct', 'ltmi_wdd_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -382,6 +384,14 @@ def lib():
         L.ltmi_ssb_plan_last_kernel.argtypes = [vp]
         L.ltmi_ssb_plan_last_kernel.restype = c.c_char_p
         L.ltmi_ssb_trotter.argtypes = [i32, vp, i64, i32, i32, vp, i32, i32, vp, i32, vp, vp]
+        L.ltmi_wdd_filter.argtypes = [i32, i32, i32, vp, vp, c.c_double, i64, i64, i32, vp, vp]
+        L.ltmi_wdd_dot.argtypes = [i32, vp, i64, i32, i32, vp, i64, i32, i32, vp, i32, vp]
+        L.ltmi_wdd_finish.argtypes = [i32, vp, i32, i32, i32, vp, vp]
+        L.ltmi_wdd_plan_create.argtypes = [i32, i32, i32, vp, i32, vp, c.c_double, c.POINTER(vp)]
+        L.ltmi_wdd_plan_destroy.argtypes = [vp]
+        L.ltmi_wdd_reconstruct.argtypes = [vp, vp, i64, vp, vp]
+        L.ltmi_wdd_plan_last_kernel.argtypes = [vp]
+        L.ltmi_wdd_plan_last_kernel.restype = c.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -1313,6 +1323,72 @@ def ssb_trotter(device, spec_ptr, ld_spec, nav_y, nav_x, idx_ptr, n_idx, sig_w, 
         int(device), spec_ptr, int(ld_spec), int(nav_y), int(nav_x), idx_ptr, int(n_idx), int(sig_w),
         geom.ctypes.data_as(ctypes.c_void_p), int(cutoff), fourier_ptr,
         stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ssb_trotter')
+
+
+def _wdd_args(window, geom):
+    """the window as 4 host int32 (y0, x0, By, Bx) and the geometry as 11 float64"""
+    window = np.ascontiguousarray(window, dtype=np.int32).reshape(-1)
+    if window.size != 4:
+        raise ValueError(f"the window holds 4 values (y0, x0, By, Bx), not {window.size}")
+    geom = np.ascontiguousarray(geom, dtype=np.float64).reshape(-1)
+    if geom.size != 11:
+        raise ValueError(f"the geometry holds 11 values (hip.ssb_geometry), not {geom.size}")
+    return window, geom
+
+
+def wdd_filter(device, nav_y, nav_x, window, geom, epsilon, q0, n_q, q_batch, filter_ptr, stream=None):
+    """The Wiener filter F of the Qs [q0, q0 + n_q) of a (nav_y, nav_x) scan -> device complex64 (n_q, By * Bx),
+    q_batch Qs per hipFFT execution; window: (y0, x0, By, Bx); geom: `ssb_geometry`.  Returns when the work is done
+    (include/ltmi.h)."""
+    window, geom = _wdd_args(window, geom)
+    check(lib().ltmi_wdd_filter(
+        int(device), int(nav_y), int(nav_x), window.ctypes.data_as(ctypes.c_void_p),
+        geom.ctypes.data_as(ctypes.c_void_p), float(epsilon), int(q0), int(n_q), int(q_batch), filter_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_wdd_filter')
+
+
+def wdd_dot(device, spec_ptr, ld_spec, nav_y, nav_x, filter_ptr, ld_filter, k0, n_k, acc_ptr, first=True, stream=None):
+    """acc[Q] (+)= sum_j G[j, Q] * F[Q, k0 + j] over n_k window pixels: complex64 half spectra as `ssb_trotter` takes
+    them, F device complex64 rows ld_filter apart, acc device float64 (nav_y * nav_x, 2) (include/ltmi.h)."""
+    check(lib().ltmi_wdd_dot(
+        int(device), spec_ptr, int(ld_spec), int(nav_y), int(nav_x), filter_ptr, int(ld_filter), int(k0), int(n_k),
+        acc_ptr, int(bool(first)), stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_wdd_dot')
+
+
+def wdd_finish(device, acc_ptr, nav_y, nav_x, n_window, fourier_ptr, stream=None):
+    """fourier[Q] = conj(S[-Q]) / |S[0, 0]|, S = acc / n_window -> device complex64 (nav_y, nav_x) (include/ltmi.h)"""
+    check(lib().ltmi_wdd_finish(
+        int(device), acc_ptr, int(nav_y), int(nav_x), int(n_window), fourier_ptr,
+        stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_wdd_finish')
+
+
+class WDDPlan(_NativePlan):
+    """Owns one `ltmi_wdd_plan*`: the Wiener filter F of every Q of the (nav_y, nav_x) scan for the window
+    (y0, x0, By, Bx) -- nav_y * nav_x * By * Bx * 8 bytes, built here --, a batched 2D R2C hipFFT over the scan for
+    min(max_batch, By * Bx) window pixels per execution and its workspace.  F that does not fit: LtmiError, code -4."""
+    _destroy, _last_kernel = 'ltmi_wdd_plan_destroy', 'ltmi_wdd_plan_last_kernel'
+
+    def __init__(self, device, nav_y, nav_x, window, max_batch, geom, epsilon):
+        window, geom = _wdd_args(window, geom)
+        out = ctypes.c_void_p()
+        check(lib().ltmi_wdd_plan_create(
+            int(device), int(nav_y), int(nav_x), window.ctypes.data_as(ctypes.c_void_p), int(max_batch),
+            geom.ctypes.data_as(ctypes.c_void_p), float(epsilon), ctypes.byref(out)), 'ltmi_wdd_plan_create')
+        self._ptr = out
+        self.device, self.nav, self.window = int(device), (int(nav_y), int(nav_x)), tuple(int(v) for v in window)
+        self.max_batch = int(max_batch)
+
+    def reconstruct(self, bf_ptr, ld_bf, fourier_ptr, stream=None):
+        """bf: device float32 (nav_y * nav_x, By * Bx), rows ld_bf elements apart; fourier: device complex64
+        (nav_y, nav_x), contiguous (include/ltmi.h)."""
+        check(lib().ltmi_wdd_reconstruct(
+            self._ptr, bf_ptr, int(ld_bf), fourier_ptr,
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_wdd_reconstruct')
+
+    def last_kernel(self):
+        """'k_transpose<4> + hipfft_r2c + k_transpose<8> + k_wdd_dot + k_wdd_finish batch=N' after the first
+        `reconstruct` call, '' before"""
+        return super().last_kernel()
 
 
 def lattice_fit(device, refineds_ptr, weights_ptr, peak_values_ptr, n_frames, n_peaks, indices_ptr, start, tolerance,

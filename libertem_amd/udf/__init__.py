@@ -10,6 +10,7 @@ from .correlation import CorrelationUDF, run_correlation
 from .peakfind import PeakFindUDF, run_peakfind, find_peaks, find_in_maps
 from .holography import HoloReconstructUDF, run_holo
 from .ssb import SSBUDF, run_ssb
+from .wdd import WDDUDF, run_wdd
 from .counting import EventCountUDF, EventStoreUDF, count_events, count_frames, estimate_thresholds
 from .orientation import (
     OrientationMatchUDF, run_orientation_match, polar_table, polar_library, polar_frames, match_polar, rotation_angles,
@@ -20,7 +21,7 @@ __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPost
            'UDFMergeAllMixin', 'UDFMeta', 'UDFRunner', 'UDFData', 'NoOpUDF', 'UDFMethod', 'check_cast', 'AutoUDF',
            'RecordUDF', 'CorrelationUDF', 'run_correlation', 'PeakFindUDF', 'run_peakfind', 'find_peaks', 'find_in_maps',
            'LatticeRefineUDF', 'run_refine', 'fit_lattice',
-           'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb',
+           'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb', 'WDDUDF', 'run_wdd',
            'EventCountUDF', 'EventStoreUDF', 'count_events', 'count_frames', 'estimate_thresholds',
            'OrientationMatchUDF', 'run_orientation_match', 'polar_table', 'polar_library', 'polar_frames',
            'match_polar', 'rotation_angles', 'UDFRunCancelled', 'UDFException']
