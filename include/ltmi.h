@@ -45,7 +45,7 @@ extern "C" {
 #define LTMI_E_INVALID (-1)      /* bad argument (null pointer, negative size, ...) */
 #define LTMI_E_DTYPE (-2)        /* dtype combination not supported */
 #define LTMI_E_SHAPE (-3)        /* shapes do not match the handle */
-#define LTMI_E_NOMEM (-4)        /* host allocation failed; a WDD filter that does not fit the device */
+#define LTMI_E_NOMEM (-4)        /* host allocation failed; a WDD filter or parallax store that does not fit */
 #define LTMI_E_RCCL_BASE 10000   /* a failing RCCL call returns LTMI_E_RCCL_BASE + ncclResult_t */
 
 /* dtype codes (numpy names) */
@@ -870,6 +870,69 @@ int ltmi_wdd_reconstruct(ltmi_wdd_plan *p, const float *bf, int64_t ld_bf, void 
 /* "k_transpose<4> + hipfft_r2c + k_transpose<8> + k_wdd_dot + k_wdd_finish batch=N" after the first
  * ltmi_wdd_reconstruct call of this plan, "" before.  The string lives as long as the plan. */
 const char *ltmi_wdd_plan_last_kernel(const ltmi_wdd_plan *p);
+
+/* ---- tilt-corrected bright-field imaging, "parallax" (hipFFT) ---------------
+ * A scan (nav_y, nav_x) and P bright-field pixels K, each with a scan image I_K and a shift sh[K] = (y, x) in scan
+ * pixels.  s(i, n) is the signed frequency of the single-sideband section, Nxc = nav_x / 2 + 1, Q = iy Nxc + ix:
+ *   G[K, Q]  = the real-to-complex transform of I_K over the scan axes (numpy.fft.rfft2), pixel-major
+ *   ey[K, iy] = exp(2 pi i (s(iy, nav_y) sh[K, 0] / nav_y)),  ex[K, ix] = exp(2 pi i (s(ix, nav_x) sh[K, 1] / nav_x))
+ *   S[Q]     = (1 / P) sum_K G[K, Q] (ey[K, iy] ex[K, ix])          float64 sums in a fixed order, cast to complex64
+ *   X[K, Q]  = G[K, Q] conj(R[Q]),  X[K, 0] = 0                      float32, every product rounded on its own
+ *   C_K      = the unnormalised complex-to-real inverse transform of X[K]: C_K[t] = sum_r I_K(r + t) ref(r)
+ *   peak     = the first maximum of C_K[ty mod nav_y, tx mod nav_x] over -m <= ty, tx <= m in row-major (ty, tx) order,
+ *              plus per axis sub(c-, c0, c+) = clip((c- - c+) / (2 d), -0.5, 0.5) if d = c- - 2 c0 + c+ < 0, else 0,
+ *              in float64 from the stored float32 neighbours (indices mod the axis)
+ * A real inverse transform takes only the Hermitian part of the columns ix = 0 and ix = nav_x / 2 of a half spectrum;
+ * the plan projects S onto it ((S[iy] + conj(S[-iy])) / 2, k_plx_herm), so that every inverse transform reads it alike.
+ * No atomics: a call repeats bit for bit.  csrc/ltmi_parallax.hip. */
+/* The ramps of n pixels: sh DEVICE float64 (n, 2) -> ey DEVICE complex128 (n, nav_y), ex DEVICE complex128 (n, Nxc).
+ * One launch of k_plx_ramps, one sincos per value.  n == 0 launches nothing.  A non-positive scan, n < 0:
+ * LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID. */
+int ltmi_plx_ramps(int device, const double *sh, int64_t n, int nav_y, int nav_x, void *ey_out, void *ex_out,
+                   void *stream);
+/* S of n pixels: spec DEVICE complex64 (n, nav_y Nxc), ey / ex as above -> s_out DEVICE complex64 (nav_y, Nxc).  One
+ * launch of k_plx_sum: the lanes run along Q, wave w of a workgroup sums the pixels [w c, (w + 1) c), c = ceil(n / 4),
+ * ascending, and the four partial sums are added in the order of the waves.  n < 1, a non-positive scan: LTMI_E_SHAPE;
+ * a null pointer: LTMI_E_INVALID. */
+int ltmi_plx_sum(int device, const void *spec, int n, int nav_y, int nav_x, const void *ey, const void *ex, void *s_out,
+                 void *stream);
+/* X of n pixels: spec DEVICE complex64 (n, nav_y Nxc), ref DEVICE complex64 (nav_y Nxc) -> x_out DEVICE complex64
+ * (n, nav_y Nxc); re = g.re r.re + g.im r.im, im = g.im r.re - g.re r.im.  One launch of k_plx_mul.  Errors as for
+ * ltmi_plx_ramps. */
+int ltmi_plx_mul(int device, const void *spec, int64_t n, int nav_y, int nav_x, const void *ref, void *x_out,
+                 void *stream);
+/* The peaks of n correlation maps: maps DEVICE float32 (n, nav_y, nav_x), contiguous -> shifts_out DEVICE float64
+ * (n, 2).  One launch of k_plx_peaks, one wave per map.  A map without a finite value gives an unspecified shift
+ * inside the window.  max_shift < 1 or > 16383, an axis shorter than 2 max_shift + 1, n < 0: LTMI_E_SHAPE; a null
+ * pointer: LTMI_E_INVALID. */
+int ltmi_plx_peaks(int device, const float *maps, int64_t n, int nav_y, int nav_x, int max_shift, double *shifts_out,
+                   void *stream);
+/* A plan owns the store of all spectra (8 n_idx nav_y Nxc bytes), the ramps (16 n_idx (nav_y + Nxc) bytes), S, one
+ * batched real-to-complex and one batched complex-to-real hipFFT of (nav_y, nav_x), min(max_batch, n_idx) pixels per
+ * execution, and per pixel of a batch a float32 scan image / correlation map and a complex64 half spectrum.  A store
+ * above store_limit_bytes or above the free device memory: LTMI_E_NOMEM, the text gives the bytes needed.  The shape
+ * errors of ltmi_plx_peaks, n_idx < 1, a batch of more than 2^31 - 1 values: LTMI_E_SHAPE; a null pointer,
+ * max_batch < 1: LTMI_E_INVALID. */
+typedef struct ltmi_plx_plan ltmi_plx_plan;   /* opaque */
+int ltmi_plx_plan_create(int device, int nav_y, int nav_x, int n_idx, int max_batch, int max_shift,
+                         int64_t store_limit_bytes, ltmi_plx_plan **out);
+int ltmi_plx_plan_destroy(ltmi_plx_plan *p);
+/* bf: device float32 (nav_y nav_x, n_idx), rows ld_bf elements apart (what ltmi_ssb_gather wrote for the whole scan)
+ * -> the store.  Per batch ltmi_transpose2d and the R2C transform.  ld_bf < n_idx: LTMI_E_SHAPE; a null pointer:
+ * LTMI_E_INVALID. */
+int ltmi_plx_plan_load(ltmi_plx_plan *p, const float *bf, int64_t ld_bf, void *stream);
+/* One iteration: shifts DEVICE float64 (n_idx, 2), read (the shifts that align the reference R = S(shifts), R[0, 0] =
+ * 0) and then overwritten with the measured ones.  k_plx_ramps, k_plx_sum, k_plx_herm, and per batch k_plx_mul, the C2R
+ * transform and k_plx_peaks.  Nothing is read back and the stream is not drained.  Before ltmi_plx_plan_load, a null
+ * pointer: LTMI_E_INVALID. */
+int ltmi_plx_plan_iterate(ltmi_plx_plan *p, double *shifts, void *stream);
+/* S(shifts), its self-paired columns Hermitian -> half_out DEVICE complex64 (nav_y, Nxc): numpy.fft.irfft2 of it is
+ * the aligned mean image.  Errors as for ltmi_plx_plan_iterate. */
+int ltmi_plx_plan_sum(ltmi_plx_plan *p, const double *shifts, void *half_out, void *stream);
+/* What the plan's last call launched: "k_transpose<4> + hipfft_r2c batch=N" (load), "k_plx_ramps + k_plx_sum +
+ * k_plx_herm + k_plx_mul + hipfft_c2r + k_plx_peaks batch=N" (iterate), "k_plx_ramps + k_plx_sum + k_plx_herm" (sum);
+ * "" before the first.  The string lives as long as the plan. */
+const char *ltmi_plx_plan_last_kernel(const ltmi_plx_plan *p);
 
 /* ---- lattice fit to the matched peaks -------------------------------------------------------------
  * Per frame, for n_peaks peaks with positions r_k = refineds[f, k] (y, x), weights w_k = weights[f, k]

@@ -67,6 +67,8 @@ EXPORTS = (
     'ltmi_ssb_plan_last_kernel', 'ltmi_ssb_trotter',
     'ltmi_wdd_filter', 'ltmi_wdd_dot', 'ltmi_wdd_finish', 'ltmi_wdd_plan_create', 'ltmi_wdd_plan_destroy',
     'ltmi_wdd_reconstruct', 'ltmi_wdd_plan_last_kernel',
+    'ltmi_plx_ramps', 'ltmi_plx_sum', 'ltmi_plx_mul', 'ltmi_plx_peaks', 'ltmi_plx_plan_create', 'ltmi_plx_plan_destroy',
+    'ltmi_plx_plan_load', 'ltmi_plx_plan_iterate', 'ltmi_plx_plan_sum', 'ltmi_plx_plan_last_kernel',
     'ltmi_csr_check', 'ltmi_csr_densify', 'ltmi_apply_masks_csr', 'ltmi_csr_max_masks',
     'ltmi_csr_sum_sig', 'ltmi_csr_sum_frames_workspace', 'ltmi_csr_sum_frames', 'ltmi_csr_last_kernel',
     'ltmi_masks_set_tuning',
@@ -392,6 +394,17 @@ def lib():
         L.ltmi_wdd_reconstruct.argtypes = [vp, vp, i64, vp, vp]
         L.ltmi_wdd_plan_last_kernel.argtypes = [vp]
         L.ltmi_wdd_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_plx_ramps.argtypes = [i32, vp, i64, i32, i32, vp, vp, vp]
+        L.ltmi_plx_sum.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp]
+        L.ltmi_plx_mul.argtypes = [i32, vp, i64, i32, i32, vp, vp, vp]
+        L.ltmi_plx_peaks.argtypes = [i32, vp, i64, i32, i32, i32, vp, vp]
+        L.ltmi_plx_plan_create.argtypes = [i32, i32, i32, i32, i32, i32, i64, c.POINTER(vp)]
+        L.ltmi_plx_plan_destroy.argtypes = [vp]
+        L.ltmi_plx_plan_load.argtypes = [vp, vp, i64, vp]
+        L.ltmi_plx_plan_iterate.argtypes = [vp, vp, vp]
+        L.ltmi_plx_plan_sum.argtypes = [vp, vp, vp, vp]
+        L.ltmi_plx_plan_last_kernel.argtypes = [vp]
+        L.ltmi_plx_plan_last_kernel.restype = c.c_char_p
         for name in EXPORTS:
             fn = getattr(L, name)
             if fn.restype is c.c_int and name not in ('ltmi_version',):
@@ -1388,6 +1401,71 @@ class WDDPlan(_NativePlan):
     def last_kernel(self):
         """'k_transpose<4> + hipfft_r2c + k_transpose<8> + k_wdd_dot + k_wdd_finish batch=N' after the first
         `reconstruct` call, '' before"""
+        return super().last_kernel()
+
+
+def _stream_arg(stream):
+    return stream if isinstance(stream, int) else _stream_ptr(stream)
+
+
+def plx_ramps(device, sh_ptr, n, nav_y, nav_x, ey_ptr, ex_ptr, stream=None):
+    """The Fourier ramps of n shifts: sh device float64 (n, 2) -> ey device complex128 (n, nav_y), ex device complex128
+    (n, nav_x // 2 + 1) (include/ltmi.h)."""
+    check(lib().ltmi_plx_ramps(int(device), sh_ptr, int(n), int(nav_y), int(nav_x), ey_ptr, ex_ptr, _stream_arg(stream)),
+          'ltmi_plx_ramps')
+
+
+def plx_sum(device, spec_ptr, n, nav_y, nav_x, ey_ptr, ex_ptr, s_ptr, stream=None):
+    """S[Q] = mean over the n pixels of G[K, Q] ey[K, iy] ex[K, ix]: spec device complex64 (n, nav_y, nav_x // 2 + 1),
+    pixel-major -> s device complex64 (nav_y, nav_x // 2 + 1) (include/ltmi.h)."""
+    check(lib().ltmi_plx_sum(int(device), spec_ptr, int(n), int(nav_y), int(nav_x), ey_ptr, ex_ptr, s_ptr,
+                             _stream_arg(stream)), 'ltmi_plx_sum')
+
+
+def plx_mul(device, spec_ptr, n, nav_y, nav_x, ref_ptr, x_ptr, stream=None):
+    """X[K, Q] = G[K, Q] conj(R[Q]) in float32, X[K, 0] = 0: spec, x device complex64 (n, nav_y, nav_x // 2 + 1), ref
+    device complex64 (nav_y, nav_x // 2 + 1) (include/ltmi.h)."""
+    check(lib().ltmi_plx_mul(int(device), spec_ptr, int(n), int(nav_y), int(nav_x), ref_ptr, x_ptr, _stream_arg(stream)),
+          'ltmi_plx_mul')
+
+
+def plx_peaks(device, maps_ptr, n, nav_y, nav_x, max_shift, shifts_ptr, stream=None):
+    """The first maximum within max_shift of the origin of n circular correlation maps, device float32
+    (n, nav_y, nav_x), refined by a parabola per axis -> device float64 (n, 2) (include/ltmi.h)."""
+    check(lib().ltmi_plx_peaks(int(device), maps_ptr, int(n), int(nav_y), int(nav_x), int(max_shift), shifts_ptr,
+                               _stream_arg(stream)), 'ltmi_plx_peaks')
+
+
+class ParallaxPlan(_NativePlan):
+    """Owns one `ltmi_plx_plan*`: the half spectra over the (nav_y, nav_x) scan of n_idx bright-field pixels --
+    8 n_idx nav_y (nav_x // 2 + 1) bytes, at most store_limit_bytes --, the ramps, a batched R2C and a batched C2R hipFFT
+    for min(max_batch, n_idx) pixels per execution and their workspace.  A store that does not fit: LtmiError, code -4."""
+    _destroy, _last_kernel = 'ltmi_plx_plan_destroy', 'ltmi_plx_plan_last_kernel'
+
+    def __init__(self, device, nav_y, nav_x, n_idx, max_batch, max_shift, store_limit_bytes):
+        out = ctypes.c_void_p()
+        check(lib().ltmi_plx_plan_create(
+            int(device), int(nav_y), int(nav_x), int(n_idx), int(max_batch), int(max_shift), int(store_limit_bytes),
+            ctypes.byref(out)), 'ltmi_plx_plan_create')
+        self._ptr = out
+        self.device, self.nav, self.n_idx = int(device), (int(nav_y), int(nav_x)), int(n_idx)
+        self.max_batch, self.max_shift = int(max_batch), int(max_shift)
+
+    def load(self, bf_ptr, ld_bf, stream=None):
+        """bf: device float32 (nav_y * nav_x, P), rows ld_bf elements apart -> the plan's spectra (include/ltmi.h)"""
+        check(lib().ltmi_plx_plan_load(self._ptr, bf_ptr, int(ld_bf), _stream_arg(stream)), 'ltmi_plx_plan_load')
+
+    def iterate(self, shifts_ptr, stream=None):
+        """shifts: device float64 (P, 2), the aligning shifts on entry, the measured ones afterwards (include/ltmi.h)"""
+        check(lib().ltmi_plx_plan_iterate(self._ptr, shifts_ptr, _stream_arg(stream)), 'ltmi_plx_plan_iterate')
+
+    def sum(self, shifts_ptr, half_ptr, stream=None):
+        """the half spectrum of the mean of the scan images aligned by `shifts` -> device complex64
+        (nav_y, nav_x // 2 + 1) (include/ltmi.h)"""
+        check(lib().ltmi_plx_plan_sum(self._ptr, shifts_ptr, half_ptr, _stream_arg(stream)), 'ltmi_plx_plan_sum')
+
+    def last_kernel(self):
+        """what the last of `load`, `iterate` and `sum` launched (include/ltmi.h), '' before the first"""
         return super().last_kernel()
 
 

@@ -11,6 +11,7 @@ from .peakfind import PeakFindUDF, run_peakfind, find_peaks, find_in_maps
 from .holography import HoloReconstructUDF, run_holo
 from .ssb import SSBUDF, run_ssb
 from .wdd import WDDUDF, run_wdd
+from .parallax import ParallaxUDF, run_parallax, parallax_bf, parallax_aberrations, fit_shifts
 from .counting import EventCountUDF, EventStoreUDF, count_events, count_frames, estimate_thresholds
 from .orientation import (
     OrientationMatchUDF, run_orientation_match, polar_table, polar_library, polar_frames, match_polar, rotation_angles,
@@ -22,6 +23,7 @@ __all__ = ['UDF', 'UDFFrameMixin', 'UDFTileMixin', 'UDFPartitionMixin', 'UDFPost
            'RecordUDF', 'CorrelationUDF', 'run_correlation', 'PeakFindUDF', 'run_peakfind', 'find_peaks', 'find_in_maps',
            'LatticeRefineUDF', 'run_refine', 'fit_lattice',
            'lattice_peaks', 'lattice_strain', 'HoloReconstructUDF', 'run_holo', 'SSBUDF', 'run_ssb', 'WDDUDF', 'run_wdd',
+           'ParallaxUDF', 'run_parallax', 'parallax_bf', 'parallax_aberrations', 'fit_shifts',
            'EventCountUDF', 'EventStoreUDF', 'count_events', 'count_frames', 'estimate_thresholds',
            'OrientationMatchUDF', 'run_orientation_match', 'polar_table', 'polar_library', 'polar_frames',
            'match_polar', 'rotation_angles', 'UDFRunCancelled', 'UDFException']

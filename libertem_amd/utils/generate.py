@@ -107,6 +107,57 @@ def weak_phase_scan(phi, step, semiconv_pix, counts=1000.):
     return frames
 
 
+def defocused_scan(obj, matrix, sig_shape, semiconv_pix, cy=None, cx=None, offset=(0, 0), counts=1000.):
+    """
+    A defocused-probe 4D-STEM scan in the geometric-optics model: the frames `libertem_amd.udf.parallax` aligns.
+
+    Detector pixel k = (ky, kx) inside the bright-field disk (ky - cy)^2 + (kx - cx)^2 < semiconv_pix^2 records the
+    scan image counts * obj(r - s_k) with s_k = matrix (k - c) + offset in scan pixels: `obj` shifted on its periodic
+    grid by a Fourier ramp with numpy.fft.fftfreq frequencies, the real part taken (at the Nyquist index of an even
+    axis a fractional shift acts as its cosine).  Pixels outside the disk are zero.  No noise is added: callers draw
+    Poisson counts from the result.
+
+    Parameters
+    ----------
+    obj : 2D array
+        the object's bright-field transmission at the scan positions (Ny, Nx), periodic
+    matrix : 2 x 2 array
+        scan pixels of shift per detector pixel of tilt, acting on (y, x)
+    sig_shape : (h, w)
+    semiconv_pix : float
+        radius of the bright-field disk in detector pixels
+    cy, cx : float or None
+        centre of the disk; None: (h / 2, w / 2)
+    offset : (float, float)
+        a shift common to all pixels
+    counts : float
+        the value of a bright-field pixel where obj = 1
+
+    Returns float64 frames of shape (Ny, Nx, h, w).
+    """
+    obj = np.asarray(obj, dtype=np.float64)
+    if obj.ndim != 2:
+        raise ValueError(f"obj must be a 2D array, not shape {obj.shape}")
+    matrix = np.asarray(matrix, dtype=np.float64)
+    if matrix.shape != (2, 2):
+        raise ValueError(f"matrix of shape {matrix.shape} must be a 2 x 2 matrix acting on (y, x)")
+    h, w = (int(s) for s in sig_shape)
+    cy = h / 2 if cy is None else float(cy)
+    cx = w / 2 if cx is None else float(cx)
+    ny, nx = obj.shape
+    y = np.arange(h, dtype=np.float64)[:, None]
+    x = np.arange(w, dtype=np.float64)[None, :]
+    inside = (y - cy) * (y - cy) + (x - cx) * (x - cx) < float(semiconv_pix) * float(semiconv_pix)
+    spectrum = np.fft.fft2(obj)
+    fy = np.fft.fftfreq(ny)[:, None]
+    fx = np.fft.fftfreq(nx)[None, :]
+    frames = np.zeros((ny, nx, h, w), np.float64)
+    for ky, kx in zip(*np.nonzero(inside)):
+        sy, sx = matrix @ np.array([ky - cy, kx - cx]) + np.asarray(offset, dtype=np.float64)
+        frames[:, :, ky, kx] = float(counts) * np.fft.ifft2(spectrum * np.exp(-2j * np.pi * (fy * sy + fx * sx))).real
+    return frames
+
+
 def electron_frames(n, shape, rate, seed, pedestal=20, noise=4, amplitude=40, spill=15, xrays=0):
     """
     Frames of a direct detector at low dose with the electron events planted at known places: what
