@@ -293,8 +293,25 @@ int64_t ltmi_logsum_workspace(int64_t n_frames, int64_t n_px, int tile_dtype);
 int ltmi_logsum_frames(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
                        int64_t ld_tile, void *out, int64_t cols, int64_t ld_out, void *workspace,
                        void *stream);
+/* WeightedSumUDF.process_tile: out[c, p] (+)= sum_n weights[n, c] * frame_n[p] -- NumPy's
+ * `weights.T @ tile.reshape((n, -1))`, the transposed mask product -- for the n_frames whole frames (n_px
+ * pixels) of `tile` and 1 <= k <= 64 components (any other k: LTMI_E_SHAPE).  `weights`: float32
+ * (n_frames, k) in device memory, ld_w >= k ELEMENTS between rows; `out`: float32, component c of tile pixel
+ * p is element c * comp_stride + (p / cols) * ld_out + p % cols; n_px % cols == 0.  accumulate = 0
+ * overwrites these elements, 1 adds to them; n_frames == 0 writes nothing either way.
+ * Exact float32 FMAs on the matrix cores (v_mfma_f32_16x16x4_f32), one chain per slab of frames, the slabs
+ * merged in float64 in a fixed order (no atomics: bitwise repeatable).  A NaN or inf pixel p of any frame
+ * makes out[:, p] non-finite (0 * NaN, as in NumPy's dense product) and touches no other pixel.
+ *   tile dtypes: bool, uint8, int8, uint16, int16, uint32, int32, float32 (others: LTMI_E_DTYPE); rows need
+ *   not be 16-byte aligned.
+ * `workspace`: device scratch of ltmi_wsum_workspace(n_frames, n_px, k) bytes -- the same for every tile
+ * dtype, at most max(256 MiB, 4 k n_px). */
+int64_t ltmi_wsum_workspace(int64_t n_frames, int64_t n_px, int k);
+int ltmi_wsum_frames(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t n_px,
+                     int64_t ld_tile, const void *weights, int k, int64_t ld_w, void *out, int64_t cols,
+                     int64_t ld_out, int64_t comp_stride, int accumulate, void *workspace, void *stream);
 
-/* merge for sig-kind buffers: dest[i] += src[i]          (src/libertem/udf/sum.py:50-52);
+/* merge for sig-kind buffers: dest[i] += src[i]         (src/libertem/udf/sum.py:50-52);
  * every dtype of enum ltmi_dtype but bool, integers wrap around like NumPy's `+=`.  LTMI_BOOL is
  * LTMI_E_DTYPE, also for ltmi_add2d: NumPy's `+=` on bool is a logical or and its `-=` an error. */
 int ltmi_axpy(int device, void *dest, const void *src, int dtype, int64_t n, void *stream);

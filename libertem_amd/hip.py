@@ -52,7 +52,7 @@ EXPORTS = (
     'ltmi_masks_nonfinite_frames',
     'ltmi_apply_masks', 'ltmi_apply_masks_rows', 'ltmi_apply_masks_shifted', 'ltmi_apply_masks_shifted_host', 'ltmi_sum_frames_workspace', 'ltmi_sum_frames', 'ltmi_sum_sig',
     'ltmi_moments_workspace', 'ltmi_moments_frames', 'ltmi_ring_moments', 'ltmi_logsum_workspace',
-    'ltmi_logsum_frames',
+    'ltmi_logsum_frames', 'ltmi_wsum_workspace', 'ltmi_wsum_frames',
     'ltmi_axpy', 'ltmi_add2d', 'ltmi_gather_rows', 'ltmi_host_device_pointer', 'ltmi_host_copy', 'ltmi_correct', 'ltmi_repair_pixels', 'ltmi_byteswap', 'ltmi_mib_decode', 'ltmi_mib_last_kernel', 'ltmi_k2is_decode', 'ltmi_frms6_decode', 'ltmi_frms6_last_kernel', 'ltmi_records_gather', 'ltmi_records_last_kernel', 'ltmi_transpose2d', 'ltmi_transpose_last_kernel', 'ltmi_com_fields', 'ltmi_fft_plan_create',
     'ltmi_fft_plan_destroy', 'ltmi_crystallinity', 'ltmi_crystallinity_corrected', 'ltmi_fft_plan_last_kernel',
     'ltmi_corr_plan_create', 'ltmi_corr_plan_destroy', 'ltmi_correlate_peaks', 'ltmi_corr_plan_last_kernel',
@@ -296,6 +296,9 @@ def lib():
         L.ltmi_logsum_workspace.argtypes = [i64, i64, i32]
         L.ltmi_logsum_workspace.restype = i64
         L.ltmi_logsum_frames.argtypes = [i32, vp, i32, i64, i64, i64, vp, i64, i64, vp, vp]
+        L.ltmi_wsum_workspace.argtypes = [i64, i64, i32]
+        L.ltmi_wsum_workspace.restype = i64
+        L.ltmi_wsum_frames.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, i64, vp, i64, i64, i64, i32, vp, vp]
         L.ltmi_axpy.argtypes = [i32, vp, vp, i32, i64, vp]
         L.ltmi_add2d.argtypes = [i32, vp, i64, vp, i64, i32, i64, i64, i32, vp]
         L.ltmi_gather_rows.argtypes = [i32, vp, i64, vp, i64, i64, vp, vp]
@@ -808,6 +811,29 @@ def logsum_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr
         int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), int(n_frames), int(n_px),
         int(ld_tile), ctypes.c_void_p(out_ptr), int(cols), int(ld_out), ctypes.c_void_p(workspace_ptr),
         _stream_ptr(stream)), 'ltmi_logsum_frames')
+
+
+#: the most components one ltmi_wsum_frames call takes
+WSUM_MAX_K = 64
+
+
+def wsum_workspace(n_frames, n_px, k):
+    return int(lib().ltmi_wsum_workspace(int(n_frames), int(n_px), int(k)))
+
+
+def wsum_frames(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, weights_ptr, k, ld_w, out_ptr,
+                comp_stride, accumulate, workspace_ptr, cols=None, ld_out=None, stream=None):
+    """out[c, p] (float32) (+)= sum over the tile's frames n of weights[n, c] * frame_n[p] (WeightedSumUDF);
+    `weights_ptr`: device float32 (n_frames, k) at leading dimension ld_w, 1 <= k <= WSUM_MAX_K; component c
+    of tile pixel p is element c * comp_stride + (p // cols) * ld_out + p % cols of `out` (default:
+    contiguous rows)"""
+    cols = n_px if cols is None else cols
+    ld_out = cols if ld_out is None else ld_out
+    check(lib().ltmi_wsum_frames(
+        int(device), ctypes.c_void_p(tile_ptr), dtype_code(tile_dtype), int(n_frames), int(n_px),
+        int(ld_tile), ctypes.c_void_p(weights_ptr), int(k), int(ld_w), ctypes.c_void_p(out_ptr), int(cols),
+        int(ld_out), int(comp_stride), 1 if accumulate else 0, ctypes.c_void_p(workspace_ptr),
+        _stream_ptr(stream)), 'ltmi_wsum_frames')
 
 
 def sum_sig(device, tile_ptr, tile_dtype, n_frames, n_px, ld_tile, out_ptr, out_dtype,

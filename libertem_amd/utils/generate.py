@@ -2,7 +2,8 @@
 
 `hologram_frame` simulates an off-axis electron hologram from an amplitude and a phase image (Lichte & Lehmann,
 Rep. Prog. Phys. 71 (2008) 016102): the frames `libertem_amd.udf.holography` reconstructs.  `weak_phase_scan` gives
-the frames of `libertem_amd.udf.ssb`, `electron_frames` those of `libertem_amd.udf.counting`.
+the frames of `libertem_amd.udf.ssb`, `electron_frames` those of `libertem_amd.udf.counting`, `mixed_phase_scan` those
+of `libertem_amd.udf.pca`.
 """
 import numpy as np
 
@@ -208,6 +209,60 @@ def electron_frames(n, shape, rate, seed, pedestal=20, noise=4, amplitude=40, sp
     indptr = np.concatenate(([0], np.cumsum(np.bincount(f, minlength=n)))).astype(np.int64)
     dark = np.full((h, w), pedestal + 0.25, dtype=np.float32)
     return frames.astype(np.uint16), dark, (indptr, p[order].astype(np.int32))
+
+
+def mixed_phase_scan(nav_shape, sig_shape, n_phases=4, seed=0, dtype='uint16', amplitude=1500., disk=40.,
+                     background=1., falloff=2.5):
+    """
+    A 4D-STEM scan of a sample of several phases with known abundances: what `libertem_amd.udf.pca` decomposes.
+
+    Every frame is a central disk of height `disk` (radius a sixth of the shorter detector edge) on a flat
+    `background`, plus `n_phases` sparse spot patterns (six single-pixel spots each, outside the disk, no pixel in
+    two patterns).  Pattern j is weighted by amplitude / falloff^j times its abundance map, a raised cosine over the
+    scan, 0.5 (1 + cos(2 pi (u_j y / ny + v_j x / nx) + phase_j)), with a different wave vector (u_j, v_j) per
+    phase: smooth maps in [0, 1], mutually different, not orthogonal.  Every pixel is drawn from the Poisson
+    distribution of that mean.
+
+    -> (frames `dtype` nav + sig, abundance_maps float64 (n_phases,) + nav, patterns float64 (n_phases,) + sig);
+    the patterns carry their amplitude, so the mean frame at scan position r is
+    background + disk + sum_j abundance_maps[j][r] * patterns[j].
+    """
+    ny, nx = (int(s) for s in nav_shape)
+    h, w = (int(s) for s in sig_shape)
+    n_phases = int(n_phases)
+    if min(ny, nx, h, w) < 1 or n_phases < 1:
+        raise ValueError(f"a scan of {(ny, nx)} frames of {(h, w)} with {n_phases} phases")
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[:h, :w].astype(np.float64)
+    r2 = (yy - h / 2) ** 2 + (xx - w / 2) ** 2
+    radius = min(h, w) / 6.0
+    base = np.full((h, w), float(background)) + float(disk) * (r2 < radius * radius)
+    free = np.flatnonzero((r2 >= (radius + 1.5) ** 2).reshape(-1))
+    n_spots = 6
+    if free.size < n_spots * n_phases:
+        raise ValueError(f"frames of {(h, w)} have no room for {n_phases} patterns of {n_spots} spots")
+    spots = rng.permutation(free)[:n_spots * n_phases].reshape((n_phases, n_spots))
+    patterns = np.zeros((n_phases, h * w))
+    for j in range(n_phases):
+        patterns[j, spots[j]] = float(amplitude) / float(falloff) ** j * rng.uniform(0.7, 1.0, n_spots)
+    patterns = patterns.reshape((n_phases, h, w))
+    sy, sx = np.mgrid[:ny, :nx].astype(np.float64)
+    # wave vectors (u, v): (1, 0), (0, 1), (1, 1), (1, -1), (2, 0), (0, 2), ... all different
+    waves = [(1, 0), (0, 1), (1, 1), (1, -1)]
+    m = 2
+    while len(waves) < n_phases:
+        waves += [(m, 0), (0, m), (m, 1), (1, m), (m, -1), (1, -m)]
+        m += 1
+    maps = np.empty((n_phases, ny, nx))
+    for j in range(n_phases):
+        u, v = waves[j]
+        maps[j] = 0.5 * (1.0 + np.cos(2 * np.pi * (u * sy / ny + v * sx / nx) + rng.uniform(0, 2 * np.pi)))
+    mean = base[None, None] + np.einsum('jyx,jhw->yxhw', maps, patterns)
+    dt = np.dtype(dtype)
+    frames = rng.poisson(mean)
+    if dt.kind in 'iu':
+        frames = np.minimum(frames, np.iinfo(dt).max)
+    return frames.astype(dt), maps, patterns
 
 
 def spot_pattern_frames(spot_lists, picks, shape, center, sigma=1.2, counts=1000., beam=200., background=2., seed=0):
