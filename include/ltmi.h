@@ -775,6 +775,53 @@ const char *ltmi_holo_plan_last_kernel(const ltmi_holo_plan *p);
 int ltmi_holo_crop(int device, const void *spec, int64_t n_frames, int h, int w, int64_t ld_spec, int out_h, int out_w,
                    int sb_y, int sb_x, const float *aperture_dev, void *g_out, int64_t ld_g, void *stream);
 
+/* ---- exit-wave power cepstrum (hipFFT) --------------------------------------
+ * For every frame, with y = (float)tile[f], all of it in float32:
+ *   t = logf(max(y, 0) + offset) * window                       (sig_h, sig_w)
+ *   C = |fft2(t)| / (sig_h sig_w)                               unshifted
+ *   out[u, v] = C[(u - out_h/2) mod sig_h, (v - out_w/2) mod sig_w] * keep[u, v]
+ * The output is centred like fftshift: quefrency (0, 0) at (out_h / 2, out_w / 2) (integer division); with
+ * out_h == sig_h and out_w == sig_w it is fftshift(C), for even and odd sizes.  keep[u, v] = 0 where
+ * hypot(u - out_h/2, v - out_w/2) < dc_radius (decided in float64 on the host), else 1.
+ * A cepstrum plan owns a batched 2D real-to-complex hipFFT of (sig_h, sig_w), `max_batch` frames per execution, its
+ * workspace (f32 frames and complex64 half spectra of one batch), the window (HOST float32 (sig_h, sig_w), copied) and
+ * scale = float32(keep / (sig_h sig_w)), divided in float64.
+ * out_h > sig_h, out_w > sig_w, a non-positive shape, a batch of more than 2^31 - 1 pixels: LTMI_E_SHAPE; a null
+ * window or `out`, max_batch < 1, an offset that is not positive and finite, dc_radius < 0 or NaN: LTMI_E_INVALID. */
+typedef struct ltmi_ceps_plan ltmi_ceps_plan;   /* opaque */
+int ltmi_ceps_plan_create(int device, int sig_h, int sig_w, int out_h, int out_w, int max_batch, float offset,
+                          const float *window_host, double dc_radius, ltmi_ceps_plan **out);
+int ltmi_ceps_plan_destroy(ltmi_ceps_plan *p);
+/* tile: device (n_frames, sig_h*sig_w) of tile_dtype (the dtypes ltmi_correlate_peaks takes), ld_tile elements apart;
+ * out: device float32 (n_frames, out_h*out_w), rows ld_out elements apart -- nothing between the rows and no row from
+ * n_frames on is written.  Per batch: k_ceps_load, R2C, k_ceps_store (csrc/ltmi_ceps.hip).  A frame with a non-finite
+ * pixel has an unspecified result; other frames are unaffected.  Negative pixels count as 0.  No atomics: the results
+ * of a call repeat bit for bit.  Nothing is read back and the stream is not drained.
+ * n_frames < 0, ld_tile < sig_h sig_w, ld_out < out_h out_w: LTMI_E_SHAPE; an unsupported tile dtype: LTMI_E_DTYPE;
+ * a null pointer: LTMI_E_INVALID.  n_frames == 0 launches nothing. */
+int ltmi_ceps_transform(ltmi_ceps_plan *p, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile,
+                        float *out, int64_t ld_out, void *stream);
+/* The kernels of the last launching ltmi_ceps_transform call of this plan:
+ * "k_ceps_load<dtype> + hipfft_r2c + k_ceps_store batch=N".  The string lives as long as the plan. */
+const char *ltmi_ceps_plan_last_kernel(const ltmi_ceps_plan *p);
+/* Step 1 alone: out[f, p] = logf(max((float)tile[f, p], 0) + offset) * window_dev[p] for p < n_px; tile: device, frames
+ * ld_tile elements apart; window_dev: DEVICE float32 (n_px); out: device float32 (n_frames, n_px), contiguous.  One
+ * launch of k_ceps_load.  n_frames < 0, n_px < 1, ld_tile < n_px: LTMI_E_SHAPE; an unsupported tile dtype:
+ * LTMI_E_DTYPE; an offset that is not positive and finite, a null pointer: LTMI_E_INVALID.  n_frames == 0 launches
+ * nothing. */
+int ltmi_ceps_load(int device, const void *tile, int tile_dtype, int64_t n_frames, int64_t ld_tile, int64_t n_px,
+                   float offset, const float *window_dev, float *out, void *stream);
+/* Step 3 alone, on half spectra the caller supplies: spec is DEVICE complex64, frame f's (h, w/2 + 1) half spectrum at
+ * spec + f * ld_spec elements.  Output element (u, v) reads ky = (u - out_h/2) mod h, kx = (v - out_w/2) mod w:
+ * spec[ky, kx] for kx <= w/2, else spec[(h - ky) mod h, w - kx] (the magnitude needs no conjugate);
+ * out = sqrt(re * re + im * im) * scale_dev[u, v] (DEVICE float32 (out_h, out_w), used as it is), every float32
+ * operation rounded on its own and the square root correctly rounded, so the result is defined bit for bit.  out:
+ * device float32, frame f at out + f * ld_out elements.  One launch of k_ceps_store.  Shape errors as for the plan, and
+ * ld_spec < h (w/2 + 1), ld_out < out_h out_w, n_frames < 0: LTMI_E_SHAPE; a null pointer: LTMI_E_INVALID.
+ * n_frames == 0 launches nothing. */
+int ltmi_ceps_store(int device, const void *spec, int64_t n_frames, int h, int w, int64_t ld_spec, int out_h, int out_w,
+                    const float *scale_dev, float *out, int64_t ld_out, void *stream);
+
 /* ---- single-sideband ptychography (hipFFT) ---------------------------------
  * For a scan of (nav_y, nav_x) positions of real frames, P bright-field pixels K listed by their row-major frame
  * index idx[K] (pixel (y, x) = (idx / sig_w, idx % sig_w)), s(i, n) the signed frequency of index i as above, and the

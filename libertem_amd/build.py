@@ -22,8 +22,8 @@ LIBDIR = os.path.join(HERE, '_lib')
 LIB = os.path.join(LIBDIR, 'libltmi.so')
 OBJDIR = os.path.join(HERE, '_lib', 'obj')
 
-SOURCES = ['ltmi_capi.cpp', 'ltmi_comm.cpp', 'ltmi_dense.hip', 'ltmi_sparse.hip', 'ltmi_reduce.hip', 'ltmi_fft.hip', 'ltmi_corr.hip', 'ltmi_holo.hip', 'ltmi_ssb.hip', 'ltmi_wdd.hip', 'ltmi_parallax.hip', 'ltmi_peakfind.hip', 'ltmi_lattice.hip', 'ltmi_dense64.hip', 'ltmi_bell.hip', 'ltmi_mib.hip', 'ltmi_split.hip', 'ltmi_scatter.hip', 'ltmi_labels.hip', 'ltmi_cryst.hip', 'ltmi_fold.hip', 'ltmi_guard.hip', 'ltmi_moments.hip', 'ltmi_framestats.hip', 'ltmi_csrframes.hip', 'ltmi_k2is.hip', 'ltmi_frms6.hip', 'ltmi_records.hip', 'ltmi_transpose.hip', 'ltmi_count.hip', 'ltmi_orient.hip', 'ltmi_wsum.hip']
-# hipFFT for the Fourier-space operators (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip, ltmi_wdd.hip, ltmi_parallax.hip).  The loader binds libhipfft.so.0 to the copy
+SOURCES = ['ltmi_capi.cpp', 'ltmi_comm.cpp', 'ltmi_dense.hip', 'ltmi_sparse.hip', 'ltmi_reduce.hip', 'ltmi_fft.hip', 'ltmi_corr.hip', 'ltmi_holo.hip', 'ltmi_ssb.hip', 'ltmi_wdd.hip', 'ltmi_parallax.hip', 'ltmi_peakfind.hip', 'ltmi_lattice.hip', 'ltmi_dense64.hip', 'ltmi_bell.hip', 'ltmi_mib.hip', 'ltmi_split.hip', 'ltmi_scatter.hip', 'ltmi_labels.hip', 'ltmi_cryst.hip', 'ltmi_fold.hip', 'ltmi_guard.hip', 'ltmi_moments.hip', 'ltmi_framestats.hip', 'ltmi_csrframes.hip', 'ltmi_k2is.hip', 'ltmi_frms6.hip', 'ltmi_records.hip', 'ltmi_transpose.hip', 'ltmi_count.hip', 'ltmi_orient.hip', 'ltmi_wsum.hip', 'ltmi_ceps.hip']
+# hipFFT for the Fourier-space operators (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip, ltmi_wdd.hip, ltmi_parallax.hip, ltmi_ceps.hip).  The loader binds libhipfft.so.0 to the copy
 # torch already has in the process (same soname), i.e. the one that matches torch's HIP runtime.
 LINK_LIBS = ['-L/opt/rocm/lib', '-lhipfft', '-ldl']
 ARCH = 'gfx950'

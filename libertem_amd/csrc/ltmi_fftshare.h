@@ -1,4 +1,4 @@
-// What the hipFFT routes share (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip, ltmi_wdd.hip).
+// What the hipFFT routes share (ltmi_fft.hip, ltmi_corr.hip, ltmi_holo.hip, ltmi_ssb.hip, ltmi_wdd.hip, ltmi_ceps.hip).
 #pragma once
 #include "ltmi_common.h"
 #include <hipfft/hipfft.h>

@@ -63,6 +63,8 @@ EXPORTS = (
     'ltmi_orient_plan_last_kernel', 'ltmi_orient_max_polar_words', 'ltmi_orient_score_block',
     'ltmi_holo_plan_create', 'ltmi_holo_plan_destroy', 'ltmi_holo_reconstruct', 'ltmi_holo_plan_last_kernel',
     'ltmi_holo_crop',
+    'ltmi_ceps_plan_create', 'ltmi_ceps_plan_destroy', 'ltmi_ceps_transform', 'ltmi_ceps_plan_last_kernel',
+    'ltmi_ceps_load', 'ltmi_ceps_store',
     'ltmi_ssb_gather', 'ltmi_ssb_plan_create', 'ltmi_ssb_plan_destroy', 'ltmi_ssb_reconstruct',
     'ltmi_ssb_plan_last_kernel', 'ltmi_ssb_trotter',
     'ltmi_wdd_filter', 'ltmi_wdd_dot', 'ltmi_wdd_finish', 'ltmi_wdd_plan_create', 'ltmi_wdd_plan_destroy',
@@ -382,6 +384,13 @@ def lib():
         L.ltmi_holo_plan_last_kernel.argtypes = [vp]
         L.ltmi_holo_plan_last_kernel.restype = c.c_char_p
         L.ltmi_holo_crop.argtypes = [i32, vp, i64, i32, i32, i64, i32, i32, i32, i32, vp, vp, i64, vp]
+        L.ltmi_ceps_plan_create.argtypes = [i32, i32, i32, i32, i32, i32, c.c_float, vp, c.c_double, c.POINTER(vp)]
+        L.ltmi_ceps_plan_destroy.argtypes = [vp]
+        L.ltmi_ceps_transform.argtypes = [vp, vp, i32, i64, i64, vp, i64, vp]
+        L.ltmi_ceps_plan_last_kernel.argtypes = [vp]
+        L.ltmi_ceps_plan_last_kernel.restype = c.c_char_p
+        L.ltmi_ceps_load.argtypes = [i32, vp, i32, i64, i64, i64, c.c_float, vp, vp, vp]
+        L.ltmi_ceps_store.argtypes = [i32, vp, i64, i32, i32, i64, i32, i32, vp, vp, i64, vp]
         L.ltmi_ssb_gather.argtypes = [i32, vp, i32, i64, i64, i64, vp, i32, vp, i64, vp]
         L.ltmi_ssb_plan_create.argtypes = [i32, i32, i32, i32, vp, i32, i32, vp, i32, c.POINTER(vp)]
         L.ltmi_ssb_plan_destroy.argtypes = [vp]
@@ -1298,6 +1307,56 @@ def holo_crop(device, spec_ptr, n_frames, h, w, ld_spec, out_h, out_w, sb_y, sb_
         int(device), spec_ptr, int(n_frames), int(h), int(w), int(ld_spec), int(out_h), int(out_w), int(sb_y),
         int(sb_x), aperture_ptr, g_ptr, int(ld_g), stream if isinstance(stream, int) else _stream_ptr(stream)),
         'ltmi_holo_crop')
+
+
+class CepstrumPlan(_NativePlan):
+    """Owns one `ltmi_ceps_plan*`: a batched 2D R2C hipFFT of (sig_h, sig_w) and its workspace, the offset added before
+    the logarithm, the window (host float32 (sig_h, sig_w)) and keep / (sig_h sig_w) for the (out_h, out_w) quefrencies
+    around the origin, `keep` clearing those closer to it than dc_radius (include/ltmi.h)."""
+    _destroy, _last_kernel = 'ltmi_ceps_plan_destroy', 'ltmi_ceps_plan_last_kernel'
+
+    def __init__(self, device, sig_h, sig_w, out_h, out_w, max_batch, offset, window, dc_radius=0.0):
+        sig = (int(sig_h), int(sig_w))
+        win = np.ascontiguousarray(window, dtype=np.float32)
+        if win.shape != sig:
+            raise ValueError(f"window of shape {win.shape} for frames of {sig}")
+        out = ctypes.c_void_p()
+        check(lib().ltmi_ceps_plan_create(
+            int(device), sig[0], sig[1], int(out_h), int(out_w), int(max_batch), float(offset),
+            win.ctypes.data_as(ctypes.c_void_p), float(dc_radius), ctypes.byref(out)), 'ltmi_ceps_plan_create')
+        self._ptr = out
+        self.device, self.sig, self.out_shape = int(device), sig, (int(out_h), int(out_w))
+        self.max_batch, self.offset, self.dc_radius = int(max_batch), float(np.float32(offset)), float(dc_radius)
+
+    def transform(self, tile_ptr, tile_dtype, n_frames, ld_tile, out_ptr, ld_out, stream=None):
+        """tile: device (n_frames, sig_h * sig_w) of tile_dtype, ld_tile elements apart; out: device float32
+        (n_frames, out_h * out_w), rows ld_out elements apart (include/ltmi.h)."""
+        check(lib().ltmi_ceps_transform(
+            self._ptr, tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), out_ptr, int(ld_out),
+            stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ceps_transform')
+
+    def last_kernel(self):
+        """'k_ceps_load<...> + hipfft_r2c + k_ceps_store batch=N' after the first launching `transform` call, ''
+        before"""
+        return super().last_kernel()
+
+
+def ceps_load(device, tile_ptr, tile_dtype, n_frames, ld_tile, n_px, offset, window_ptr, out_ptr, stream=None):
+    """The first kernel of `CepstrumPlan.transform` alone: out[f, p] = logf(max(tile[f, p], 0) + offset) * window[p];
+    tile: device, frames ld_tile elements apart; window: device float32 (n_px); out: device float32 (n_frames, n_px),
+    contiguous (include/ltmi.h)."""
+    check(lib().ltmi_ceps_load(
+        int(device), tile_ptr, dtype_code(tile_dtype), int(n_frames), int(ld_tile), int(n_px), float(offset),
+        window_ptr, out_ptr, stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ceps_load')
+
+
+def ceps_store(device, spec_ptr, n_frames, h, w, ld_spec, out_h, out_w, scale_ptr, out_ptr, ld_out, stream=None):
+    """The last kernel of `CepstrumPlan.transform` on complex64 half spectra the caller supplies: frame f's
+    (h, w // 2 + 1) half spectrum at spec + f * ld_spec elements, the float32 scale (out_h, out_w) on the device, used
+    as it is; frame f's float32 (out_h, out_w) result at out + f * ld_out elements (include/ltmi.h)."""
+    check(lib().ltmi_ceps_store(
+        int(device), spec_ptr, int(n_frames), int(h), int(w), int(ld_spec), int(out_h), int(out_w), scale_ptr, out_ptr,
+        int(ld_out), stream if isinstance(stream, int) else _stream_ptr(stream)), 'ltmi_ceps_store')
 
 
 def ssb_geometry(lamb, dpix, semiconv, semiconv_pix, cy, cx, transformation):

@@ -3,7 +3,7 @@
 `hologram_frame` simulates an off-axis electron hologram from an amplitude and a phase image (Lichte & Lehmann,
 Rep. Prog. Phys. 71 (2008) 016102): the frames `libertem_amd.udf.holography` reconstructs.  `weak_phase_scan` gives
 the frames of `libertem_amd.udf.ssb`, `electron_frames` those of `libertem_amd.udf.counting`, `mixed_phase_scan` those
-of `libertem_amd.udf.pca`.
+of `libertem_amd.udf.pca`, `strained_lattice_scan` those of `libertem_amd.udf.cepstrum`.
 """
 import numpy as np
 
@@ -263,6 +263,73 @@ def mixed_phase_scan(nav_shape, sig_shape, n_phases=4, seed=0, dtype='uint16', a
     if dt.kind in 'iu':
         frames = np.minimum(frames, np.iinfo(dt).max)
     return frames.astype(dt), maps, patterns
+
+
+def strained_lattice_scan(nav_shape, sig_shape, a, b, strain=None, modulation=0.6, counts=1000., envelope=0.35,
+                          dtype='uint16'):
+    """
+    Nanobeam diffraction patterns of a lattice under a known strain field: what `libertem_amd.udf.cepstrum` transforms.
+
+    With r = ((i - h / 2) / h, (j - w / 2) / w) for pixel (i, j), frame n is
+
+        counts * exp(-(((i - h / 2) / (envelope h))^2 + ((j - w / 2) / (envelope w))^2) / 2)
+               * exp(modulation * (cos(2 pi a_n . r) + cos(2 pi b_n . r)))
+
+    a slowly varying envelope times a lattice-periodic part.  a_n = (1 + eps_n) a and b_n = (1 + eps_n) b are the
+    real-space lattice vectors (y, x) in pixels of the cepstrum, eps_n the 2 x 2 strain tensor of scan position n:
+    the logarithm of the frame is a parabola plus two cosines, so its cepstral peaks lie at +-a_n and +-b_n.
+
+    Parameters
+    ----------
+    nav_shape, sig_shape : tuples of int
+        scan shape; (h, w)
+    a, b : (float, float)
+        the unstrained lattice vectors
+    strain : array of shape nav_shape + (2, 2), or None
+        eps_n, acting on (y, x); None: no strain
+    modulation : float
+        depth of the lattice-periodic part in the logarithm
+    counts : float
+        height of the envelope
+    envelope : float
+        width (sigma) of the envelope as a fraction of the frame edge
+    dtype : dtype
+        integer dtypes are rounded with rint (and must hold counts * exp(2 modulation))
+
+    Returns (frames `dtype` nav_shape + (h, w), a_n float64 nav_shape + (2,), b_n float64 nav_shape + (2,)).
+    """
+    nav = tuple(int(s) for s in nav_shape)
+    h, w = (int(s) for s in sig_shape)
+    if min(nav + (h, w)) < 1:
+        raise ValueError(f"a scan of {nav} frames of {(h, w)}")
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.shape != (2,) or b.shape != (2,):
+        raise ValueError(f"a {a.shape} and b {b.shape} must be two vectors (y, x)")
+    if strain is None:
+        strain = np.zeros(nav + (2, 2))
+    strain = np.asarray(strain, dtype=np.float64)
+    if strain.shape != nav + (2, 2):
+        raise ValueError(f"strain of shape {strain.shape} for a scan of {nav}: not {nav + (2, 2)}")
+    if envelope <= 0:
+        raise ValueError(f"envelope {envelope} must be positive")
+    distortion = np.eye(2) + strain
+    a_n = distortion @ a
+    b_n = distortion @ b
+    ry = ((np.arange(h, dtype=np.float64) - h / 2) / h)[:, None]
+    rx = ((np.arange(w, dtype=np.float64) - w / 2) / w)[None, :]
+    smooth = float(counts) * np.exp(-((ry / envelope) ** 2 + (rx / envelope) ** 2) / 2)
+
+    def phase(vec):
+        return 2 * np.pi * (vec[..., 0, None, None] * ry + vec[..., 1, None, None] * rx)
+
+    frames = smooth * np.exp(float(modulation) * (np.cos(phase(a_n)) + np.cos(phase(b_n))))
+    dt = np.dtype(dtype)
+    if dt.kind in 'iu':
+        frames = np.rint(frames)
+        if frames.max() > np.iinfo(dt).max:
+            raise ValueError(f"counts {counts} * exp(2 * {modulation}) does not fit {dt}")
+    return frames.astype(dt), a_n, b_n
 
 
 def spot_pattern_frames(spot_lists, picks, shape, center, sigma=1.2, counts=1000., beam=200., background=2., seed=0):
