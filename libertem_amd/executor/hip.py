@@ -247,12 +247,10 @@ class HipJobExecutor(JobExecutor):
     def close(self):
         self._scattered = {}
         if self.gpu_id is not None:
-            # the reconstruction plans SSBUDF.get_results, WDDUDF.get_results and ParallaxUDF.get_results cached for
-            # this device, with their workspace (and the filters and spectra) in HBM
-            from libertem_amd.udf import parallax, ssb, wdd
-            ssb.release_plans(self.gpu_id)
-            wdd.release_plans(self.gpu_id)
-            parallax.release_plans(self.gpu_id)
+            # the reconstruction plans the scan UDFs' get_results cached for this device, with their workspace (and
+            # the filters and spectra) in HBM
+            from libertem_amd.udf.plans import release_device_plans
+            release_device_plans(self.gpu_id)
         if getattr(self, '_comm_state', None):
             self._comm_state.close()
             self._comm_state = None

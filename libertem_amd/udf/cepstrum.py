@@ -26,15 +26,13 @@ for the mean cepstrum, `find_peaks` on it, `run_correlation` and `run_refine` fo
 cepstral virtual detectors, `run_pca`.
 Not part of this module: the power cepstrum |F(log |F|^2)|^2, a running mean over frames, peak tracking itself.
 """
-import hashlib
-
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.correlation import CORR_WORKSPACE_BYTES
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES, PlanCache, array_digest, frame_batch, udf_device
 
-_PLANS = {}          # (device, h, w, oh, ow, batch, offset, dc_radius, digest of the window) -> hip.CepstrumPlan
+# (device, h, w, oh, ow, batch, offset, dc_radius, digest of the window) -> hip.CepstrumPlan
+_PLANS = PlanCache(8, owned=False)
 
 
 def hann_window(sig):
@@ -114,27 +112,20 @@ def cepstrum_frames(frames, out_shape, offset=1.0, window=None, dc_radius=0.0, d
 def _plan(device, sig, out_shape, batch, offset, window, dc_radius):
     from libertem_amd import hip
     key = (int(device), sig[0], sig[1], out_shape[0], out_shape[1], int(batch), float(offset), float(dc_radius),
-           hashlib.sha1(window.tobytes()).hexdigest())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 8:
-            _PLANS.clear()          # (a plan goes with its last user: kept task instances may still hold one)
-        plan = _PLANS[key] = hip.CepstrumPlan(device, sig[0], sig[1], out_shape[0], out_shape[1], batch, offset,
-                                              window, dc_radius)
-    return plan
+           array_digest(window))
+    return _PLANS.get_or_make(key, lambda: hip.CepstrumPlan(device, sig[0], sig[1], out_shape[0], out_shape[1], batch,
+                                                            offset, window, dc_radius))
 
 
 def plan_for(udf, sig, out_shape, offset, window, dc_radius):
     """the cached plan of a UDF's device, shapes, offset, window, dc_radius and batch: as many frames as the workspace
     budget (the one measured for correlation plans), the tile depth and the partition allow"""
-    device = udf.meta.gpu_id if udf.meta.gpu_id is not None else 0
     per_frame = 4 * sig[0] * sig[1] + 8 * sig[0] * (sig[1] // 2 + 1)
-    depth = int(udf.meta.tiling_scheme.depth) if udf.meta.tiling_scheme is not None else 1
-    batch = max(1, min(CORR_WORKSPACE_BYTES // per_frame, depth, int(udf.meta.partition_shape[0])))
-    return _plan(device, sig, out_shape, batch, offset, window, dc_radius)
+    batch = frame_batch(udf, per_frame, CORR_WORKSPACE_BYTES)
+    return _plan(udf_device(udf), sig, out_shape, batch, offset, window, dc_radius)
 
 
-class CepstrumUDF(UDF):
+class CepstrumUDF(WholeFrameUDF):
     """
     Parameters
     ----------
@@ -150,20 +141,8 @@ class CepstrumUDF(UDF):
     Result (nav, on the device): 'cepstrum' (float32, `out_shape`).
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, out_shape, offset=1.0, window=None, dc_radius=0.0):
         super().__init__(out_shape=tuple(out_shape), offset=offset, window=window, dc_radius=dc_radius)
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
 
     def get_result_buffers(self):
         out_shape = tuple(int(s) for s in self.params.out_shape)
@@ -182,20 +161,15 @@ class CepstrumUDF(UDF):
             td.update(plan=plan_for(self, sig, out_shape, offset, window, dc_radius))
         return td
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
+    def _process_tile_numpy(self, tile):
         td = self.task_data
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self.results.cepstrum[:] = cepstrum_frames(np.asarray(tile), td.out_shape, td.offset, td.window,
-                                                       td.dc_radius)
-            return
+        self.results.cepstrum[:] = cepstrum_frames(np.asarray(tile), td.out_shape, td.offset, td.window, td.dc_radius)
+
+    def _process_tile_hip(self, tile):
         ceps = self.results.cepstrum
         check_device_args(self, tile, ceps)
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"CepstrumUDF transforms whole frames {td.sig}, got tiles of {tile.shape[1:]}")
-        td.plan.transform(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, ceps.data_ptr(), ceps.ld,
-                          stream=self.meta.stream_ptr)
+        self.task_data.plan.transform(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, ceps.data_ptr(), ceps.ld,
+                                      stream=self.meta.stream_ptr)
 
 
 def run_cepstrum(ctx, dataset, out_shape, offset=1.0, window=None, dc_radius=0.0, roi=None):

@@ -20,39 +20,25 @@ A frame with a non-finite pixel has peak_values NaN for every peak; its other re
 On the device a whole tile goes through two batched hipFFTs and three kernels (`ltmi_correlate_peaks`,
 csrc/ltmi_corr.hip); on a CPU executor NumPy computes the definition in float64 and casts at the end.
 """
-import hashlib
-
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES, PlanCache, array_digest, frame_batch, udf_device
 
-#: workspace budget of one plan (f32 frames + complex64 half spectra of one batch), bytes.  Measured on 16 384 frames
-#: of 256 x 256 (profiles/correlation.txt): batches of 32 / 128 / 255 / 1020 frames take 34.8 / 17.5 / 15.0 / 14.0 ms --
-#: the transforms of a small batch do not fill the chip, and a batch that fits the Infinity Cache gains nothing
-CORR_WORKSPACE_BYTES = 512 * 2**20
-_PLANS = {}          # (device, h, w, batch, template digest) -> hip.CorrPlan
+_PLANS = PlanCache(8, owned=False)          # (device, h, w, batch, template digest) -> hip.CorrPlan
 
 
 def _plan(device, sig, batch, template):
     from libertem_amd import hip
-    key = (int(device), int(sig[0]), int(sig[1]), int(batch), hashlib.sha1(template.tobytes()).hexdigest())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 8:
-            _PLANS.clear()          # (a plan goes with its last user: kept task instances may still hold one)
-        plan = _PLANS[key] = hip.CorrPlan(device, sig[0], sig[1], batch, template)
-    return plan
+    key = (int(device), int(sig[0]), int(sig[1]), int(batch), array_digest(template))
+    return _PLANS.get_or_make(key, lambda: hip.CorrPlan(device, sig[0], sig[1], batch, template))
 
 
 def plan_for(udf, sig, template):
     """the cached plan of a UDF's device, frame shape, template and batch: as many frames as the workspace budget,
     the tile depth and the partition allow"""
-    device = udf.meta.gpu_id if udf.meta.gpu_id is not None else 0
     per_frame = sig[0] * sig[1] * 4 + sig[0] * (sig[1] // 2 + 1) * 8
-    depth = int(udf.meta.tiling_scheme.depth) if udf.meta.tiling_scheme is not None else 1
-    batch = max(1, min(CORR_WORKSPACE_BYTES // per_frame, depth, int(udf.meta.partition_shape[0])))
-    return _plan(device, sig, batch, template)
+    return _plan(udf_device(udf), sig, frame_batch(udf, per_frame, CORR_WORKSPACE_BYTES), template)
 
 
 def _window(p, radius, size):
@@ -100,7 +86,7 @@ def correlate_frames(frames, template, peaks, crop_radius, refine_radius=1):
     return centers, refineds, values, elevations
 
 
-class CorrelationUDF(UDF):
+class CorrelationUDF(WholeFrameUDF):
     """
     Parameters
     ----------
@@ -117,20 +103,8 @@ class CorrelationUDF(UDF):
     and 'peak_elevations' (float32, (n_peaks,)).
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, peaks, template, crop_radius, refine_radius=1):
         super().__init__(peaks=peaks, template=template, crop_radius=crop_radius, refine_radius=refine_radius)
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
 
     def _peaks(self):
         peaks = np.asarray(self.params.peaks)
@@ -172,13 +146,8 @@ class CorrelationUDF(UDF):
         return td
 
     def process_tile(self, tile):
-        n = tile.shape[0]
-        if n == 0 or len(self.task_data.peaks) == 0:
-            return
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self._process_tile_numpy(tile)
-        else:
-            self._process_tile_hip(tile)
+        if len(self.task_data.peaks):
+            super().process_tile(tile)
 
     def _process_tile_numpy(self, tile):
         td = self.task_data
@@ -192,8 +161,6 @@ class CorrelationUDF(UDF):
         r = self.results
         check_device_args(self, tile, r.centers, r.refineds, r.peak_values, r.peak_elevations)
         td = self.task_data
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"CorrelationUDF transforms whole frames {td.sig}, got tiles of {tile.shape[1:]}")
         peaks = td.device_peaks.get(tile.device)
         if peaks is None:
             import torch

@@ -34,8 +34,8 @@ import numpy as np
 
 from libertem_amd.common.hiparray import HipArray
 from libertem_amd.common.math import prod
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.device import check_device_args, check_whole_frames, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, runs_on_hip
+from libertem_amd.udf.plans import udf_device
 
 #: frame dtypes that are counted (what `ltmi_count_events` takes)
 FRAME_DTYPES = tuple(np.dtype(t) for t in ('u1', 'i1', 'u2', 'i2', 'u4', 'i4', 'f4'))
@@ -158,19 +158,9 @@ def estimate_thresholds(frames, dark=None, gain=None, background_sigma=4.0, xray
     return med + float(background_sigma) * 1.4826 * mad, t_x
 
 
-class _CountingUDF(UDF):
-    """what the two UDFs share: the parameter checks and the device copies of dark and gain"""
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame have no events
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
+class _CountingUDF(WholeFrameUDF):
+    """what the two UDFs share: the parameter checks and the device copies of dark and gain (positions a sync_offset
+    leaves without a frame have no events)"""
 
     def _counting_task_data(self, values='count'):
         check_whole_frames(self)
@@ -184,8 +174,7 @@ class _CountingUDF(UDF):
         if runs_on_hip(self):
             if sig[1] > MAX_WIDTH:
                 raise ValueError(f"frames of {sig[1]} columns: the device counts frames of at most {MAX_WIDTH}")
-            device = self.meta.gpu_id if self.meta.gpu_id is not None else 0
-            td['device'] = device
+            device = td['device'] = udf_device(self)
             if dark is not None:
                 td['dark_dev'] = HipArray.from_numpy(dark, device)
             if gain is not None:
@@ -195,8 +184,6 @@ class _CountingUDF(UDF):
     def _kernel_args(self, tile):
         """the leading arguments of `hip.count_events` / `hip.store_events` for a device tile"""
         td = self.task_data
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"{type(self).__name__} counts whole frames {td.sig}, got tiles of {tile.shape[1:]}")
         check_frame_dtype(tile.dtype)
         return (td.device, tile.data_ptr(), tile.dtype, tile.shape[0], td.sig[0], td.sig[1], tile.ld,
                 td.dark_dev.data_ptr() if td.dark_dev is not None else None,
@@ -233,14 +220,12 @@ class EventCountUDF(_CountingUDF):
     def get_task_data(self):
         return self._counting_task_data()
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
+    def _process_tile_numpy(self, tile):
         td = self.task_data
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            indptr, _, _ = count_frames(np.asarray(tile), td.t_bg, td.t_x, td.dark, td.gain)
-            self.results.n_events[:] = np.diff(indptr).astype(np.int32)
-            return
+        indptr, _, _ = count_frames(np.asarray(tile), td.t_bg, td.t_x, td.dark, td.gain)
+        self.results.n_events[:] = np.diff(indptr).astype(np.int32)
+
+    def _process_tile_hip(self, tile):
         from libertem_amd import hip
         check_device_args(self, tile, self.results.n_events)
         hip.count_events(*self._kernel_args(tile), self.results.n_events.data_ptr(), stream=self.meta.stream_ptr)
@@ -302,29 +287,27 @@ class EventStoreUDF(_CountingUDF):
             td['indptr_dev'] = HipArray.from_numpy(indptr, td['device'])
         return td
 
-    def process_tile(self, tile):
-        n = tile.shape[0]
-        if n == 0:
-            return
-        td = self.task_data
+    def _span(self, tile):
+        """-> the tile's first frame, and where its events begin and end in the two files"""
         first = int(self.meta.slice.origin[0])
-        lo, hi = int(td.indptr[first]), int(td.indptr[first + n])
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            indptr, indices, data = count_frames(np.asarray(tile), td.t_bg, td.t_x, td.dark, td.gain,
-                                                 self._kwargs['values'])
-            if not np.array_equal(indptr + lo, td.indptr[first:first + n + 1]):
-                raise RuntimeError(f"indptr does not fit the events of the frames from {first} on")
-            if hi > lo:
-                td.indices[lo:hi] = indices
-                td.data[lo:hi] = data
-            return
-        self._store_hip(tile, first, lo, hi)
+        return first, int(self.task_data.indptr[first]), int(self.task_data.indptr[first + tile.shape[0]])
 
-    def _store_hip(self, tile, first, lo, hi):
+    def _process_tile_numpy(self, tile):
+        td = self.task_data
+        first, lo, hi = self._span(tile)
+        indptr, indices, data = count_frames(np.asarray(tile), td.t_bg, td.t_x, td.dark, td.gain,
+                                             self._kwargs['values'])
+        if not np.array_equal(indptr + lo, td.indptr[first:first + tile.shape[0] + 1]):
+            raise RuntimeError(f"indptr does not fit the events of the frames from {first} on")
+        if hi > lo:
+            td.indices[lo:hi] = indices
+            td.data[lo:hi] = data
+
+    def _process_tile_hip(self, tile):
         import torch
         from libertem_amd import hip
-        check_device_args(self, tile)
         td = self.task_data
+        first, lo, hi = self._span(tile)
         nnz, isz = hi - lo, td.vdtype.itemsize
         # one buffer, one copy: [indices int32 x nnz | values x nnz | padding to 4 bytes | status int32]
         at_values = 4 * nnz

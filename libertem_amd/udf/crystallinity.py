@@ -13,12 +13,13 @@ from libertem_amd.common.exceptions import HipRequiredError
 from libertem_amd.masks import _make_circular_mask
 from libertem_amd.udf.base import UDF, UDFMethod
 from libertem_amd.udf.device import check_device_args
+from libertem_amd.udf.plans import PlanCache, frame_batch, udf_device
 
 #: workspace budget of one plan (f32 frames + complex64 half spectra), bytes: created only when a route needs it
 #: (hipFFT, corrected frames, the column workspace of 512 / 1024-pixel frames) -- frames of 1024 x 1024 want ~250 per
 #: pass of the workspace to fill the chip (one workgroup per frame in the column kernel)
 FFT_WORKSPACE_BYTES = 2 * 2**30
-_PLANS = {}          # (device, h, w, batch) -> hip.FFTPlan
+_PLANS = PlanCache(8, owned=False)          # (device, h, w, batch) -> hip.FFTPlan
 _MASKS = {}          # (device, sig, params) -> (real_mask tensor | None, half mask tensor)
 
 
@@ -59,14 +60,7 @@ def mask_box(half):
 def _plan(device, sig, batch):
     from libertem_amd import hip
     key = (int(device), int(sig[0]), int(sig[1]), int(batch))
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 8:
-            for old in list(_PLANS.values()):
-                old.close()
-            _PLANS.clear()
-        plan = _PLANS[key] = hip.FFTPlan(device, sig[0], sig[1], batch)
-    return plan
+    return _PLANS.get_or_make(key, lambda: hip.FFTPlan(device, sig[0], sig[1], batch))
 
 
 class CrystallinityUDF(UDF):
@@ -105,7 +99,7 @@ class CrystallinityUDF(UDF):
         sig = tuple(self.meta.partition_shape.sig)
         if len(sig) != 2:
             raise ValueError("CrystallinityUDF needs 2D frames")
-        device = self.meta.gpu_id if self.meta.gpu_id is not None else 0
+        device = udf_device(self)
         p = self.params
         rc = None if p.real_center is None else tuple(float(x) for x in p.real_center)
         key = (device, sig, float(p.rad_in), float(p.rad_out), rc,
@@ -122,9 +116,7 @@ class CrystallinityUDF(UDF):
                 _MASKS.clear()
             hit = _MASKS[key] = (rm, hm, mask_box(half))
         per_frame = sig[0] * sig[1] * 4 + sig[0] * (sig[1] // 2 + 1) * 8
-        depth = int(self.meta.tiling_scheme.depth) if self.meta.tiling_scheme is not None else 1
-        batch = max(1, min(FFT_WORKSPACE_BYTES // per_frame, depth,
-                           int(self.meta.partition_shape[0])))
+        batch = frame_batch(self, per_frame, FFT_WORKSPACE_BYTES)
         return {'real_mask': hit[0], 'half_mask': hit[1], 'box': hit[2],
                 'plan': _plan(device, sig, batch), 'sig': sig}
 

@@ -1,8 +1,11 @@
 """
-What the reduction UDFs that run on the device share (SumUDF, SumSigUDF, StdDevUDF, FEMUDF,
+What the UDFs that run on the device share.  For the reduction UDFs (SumUDF, SumSigUDF, StdDevUDF, FEMUDF,
 LogsumUDF): the backend and argument checks, the scratch buffer of a task, where a tile's sig slice
-lies in the full-frame buffer, and the float frames of the NumPy branches.  Plain functions and two
-small classes; the UDFs derive from `UDF` directly, as the reference's do.
+lies in the full-frame buffer, and the float frames of the NumPy branches -- plain functions and two
+small classes; those UDFs derive from `UDF` directly, as the reference's do.  For the UDFs that take
+whole frames of every valid position, on the device or in NumPy (correlation, peak search, holography,
+cepstrum, orientation matching, event counting, the scan UDFs of `libertem_amd.udf.ssb`): the base
+class `WholeFrameUDF`.
 """
 import contextlib
 import warnings
@@ -12,6 +15,7 @@ import numpy as np
 from libertem_amd.common.math import prod
 from libertem_amd.common.hiparray import HipArray
 from libertem_amd.common.exceptions import HipRequiredError
+from libertem_amd.udf.base import UDF
 
 
 def runs_on_hip(udf):
@@ -41,6 +45,37 @@ def check_whole_frames(udf):
         raise ValueError(
             f"{type(udf).__name__} needs whole frames, but the dataset forces tileshape {shape} that cuts "
             f"the frames of shape {ds_shape[-len(tuple(udf.meta.dataset_shape.sig)):]}")
+
+
+class WholeFrameUDF(UDF):
+    """A UDF of whole frames in their stored dtype, on BACKEND_HIP or BACKEND_NUMPY.  A subclass calls
+    `check_whole_frames` and puts the frame shape `sig` into its task data, and processes the tiles,
+    none of them empty, in `_process_tile_numpy(tile)` and `_process_tile_hip(tile)`."""
+
+    REUSE_TASK_INSTANCES = True
+    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
+    VALID_FRAMES_ONLY = True
+    WHOLE_FRAME_TILES = True
+
+    def get_preferred_input_dtype(self):
+        # the frames as stored: the kernels convert in registers
+        return self.USE_NATIVE_DTYPE
+
+    def get_backends(self):
+        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
+
+    def process_tile(self, tile):
+        if tile.shape[0] == 0:
+            return
+        if self.meta.array_backend == self.BACKEND_NUMPY:
+            self._process_tile_numpy(tile)
+            return
+        check_device_args(self, tile)
+        sig = tuple(self.task_data.sig)
+        if tuple(tile.shape[1:]) != sig:
+            raise ValueError(
+                f"{type(self).__name__} takes whole frames {sig}, got tiles of {tuple(tile.shape[1:])}")
+        self._process_tile_hip(tile)
 
 
 class Workspace:

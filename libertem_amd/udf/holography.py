@@ -20,15 +20,13 @@ On the device a whole tile goes through two batched hipFFTs and three kernels (`
 csrc/ltmi_holo.hip); on a CPU executor NumPy computes the definition in float64 / complex128 and casts at the end.
 Not part of this module: line filters (multiply them into `aperture`), averaging over a series, phase unwrapping.
 """
-import hashlib
-
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.correlation import CORR_WORKSPACE_BYTES
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES, PlanCache, array_digest, frame_batch, udf_device
 
-_PLANS = {}          # (device, h, w, oh, ow, batch, sy, sx, digest of aperture and reference) -> hip.HoloPlan
+# (device, h, w, oh, ow, batch, sy, sx, digest of aperture and reference) -> hip.HoloPlan
+_PLANS = PlanCache(8, owned=False)
 
 
 def signed_frequencies(n):
@@ -123,30 +121,21 @@ def reconstruct_frames(frames, out_shape, sb_position, aperture, reference_wave=
 
 def _plan(device, sig, out_shape, batch, sb, aperture, reference_wave):
     from libertem_amd import hip
-    digest = hashlib.sha1(aperture.tobytes())
-    if reference_wave is not None:
-        digest.update(b'ref' + np.ascontiguousarray(reference_wave).tobytes())
-    key = (int(device), sig[0], sig[1], out_shape[0], out_shape[1], int(batch), sb[0], sb[1], digest.hexdigest())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 8:
-            _PLANS.clear()          # (a plan goes with its last user: kept task instances may still hold one)
-        plan = _PLANS[key] = hip.HoloPlan(device, sig[0], sig[1], out_shape[0], out_shape[1], batch, sb[0], sb[1],
-                                          aperture, reference_wave)
-    return plan
+    key = (int(device), sig[0], sig[1], out_shape[0], out_shape[1], int(batch), sb[0], sb[1],
+           array_digest(aperture, reference_wave))
+    return _PLANS.get_or_make(key, lambda: hip.HoloPlan(device, sig[0], sig[1], out_shape[0], out_shape[1], batch,
+                                                        sb[0], sb[1], aperture, reference_wave))
 
 
 def plan_for(udf, sig, out_shape, sb, aperture, reference_wave):
     """the cached plan of a UDF's device, shapes, sideband, aperture, reference and batch: as many frames as the
     workspace budget (the one measured for correlation plans), the tile depth and the partition allow"""
-    device = udf.meta.gpu_id if udf.meta.gpu_id is not None else 0
     per_frame = 4 * sig[0] * sig[1] + 8 * sig[0] * (sig[1] // 2 + 1) + 8 * out_shape[0] * out_shape[1]
-    depth = int(udf.meta.tiling_scheme.depth) if udf.meta.tiling_scheme is not None else 1
-    batch = max(1, min(CORR_WORKSPACE_BYTES // per_frame, depth, int(udf.meta.partition_shape[0])))
-    return _plan(device, sig, out_shape, batch, sb, aperture, reference_wave)
+    batch = frame_batch(udf, per_frame, CORR_WORKSPACE_BYTES)
+    return _plan(udf_device(udf), sig, out_shape, batch, sb, aperture, reference_wave)
 
 
-class HoloReconstructUDF(UDF):
+class HoloReconstructUDF(WholeFrameUDF):
     """
     Parameters
     ----------
@@ -167,11 +156,6 @@ class HoloReconstructUDF(UDF):
     Result (nav, on the device): 'wave' (complex64, `out_shape`).
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, out_shape, sb_position, aperture=None, sb_size=None, sb_smoothness=0.0, reference_wave=None):
         if aperture is None:
             if sb_size is None:
@@ -179,13 +163,6 @@ class HoloReconstructUDF(UDF):
             aperture = disk_aperture(out_shape, sb_size, sb_smoothness)
         super().__init__(out_shape=tuple(out_shape), sb_position=tuple(sb_position), aperture=aperture, sb_size=sb_size,
                          sb_smoothness=sb_smoothness, reference_wave=reference_wave)
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
 
     def get_result_buffers(self):
         out_shape = tuple(int(s) for s in self.params.out_shape)
@@ -205,20 +182,16 @@ class HoloReconstructUDF(UDF):
             td.update(plan=plan_for(self, sig, out_shape, sb, aperture, reference_wave))
         return td
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
+    def _process_tile_numpy(self, tile):
         td = self.task_data
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self.results.wave[:] = reconstruct_frames(np.asarray(tile), td.out_shape, td.sb, td.aperture,
-                                                      td.reference_wave)
-            return
+        self.results.wave[:] = reconstruct_frames(np.asarray(tile), td.out_shape, td.sb, td.aperture,
+                                                  td.reference_wave)
+
+    def _process_tile_hip(self, tile):
         wave = self.results.wave
         check_device_args(self, tile, wave)
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"HoloReconstructUDF transforms whole frames {td.sig}, got tiles of {tile.shape[1:]}")
-        td.plan.reconstruct(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, wave.data_ptr(), wave.ld,
-                            stream=self.meta.stream_ptr)
+        self.task_data.plan.reconstruct(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, wave.data_ptr(), wave.ld,
+                                        stream=self.meta.stream_ptr)
 
 
 def run_holo(ctx, dataset, out_shape, sb_position, aperture=None, sb_size=None, sb_smoothness=0.0,

@@ -175,20 +175,21 @@ class LatticeRefineUDF(CorrelationUDF):
         td.update(indices=idx, start=start, tol=tol, device_indices={})
         return td
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
-        super().process_tile(tile)
+    def _process_tile_numpy(self, tile):
+        super()._process_tile_numpy(tile)
         td, r = self.task_data, self.results
         weighted = bool(self.params.weighted)
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            res = fit_lattice(np.asarray(r.refineds), np.asarray(r.peak_elevations) if weighted else None,
-                              None if weighted else np.asarray(r.peak_values), td.indices, td.start[0:2],
-                              td.start[2:4], td.start[4:6], td.tol)
-            for name, value in zip(LATTICE_NAMES, res):
-                getattr(r, name)[:] = value
-            return
+        res = fit_lattice(np.asarray(r.refineds), np.asarray(r.peak_elevations) if weighted else None,
+                          None if weighted else np.asarray(r.peak_values), td.indices, td.start[0:2],
+                          td.start[2:4], td.start[4:6], td.tol)
+        for name, value in zip(LATTICE_NAMES, res):
+            getattr(r, name)[:] = value
+
+    def _process_tile_hip(self, tile):
+        super()._process_tile_hip(tile)
         from libertem_amd import hip
+        td, r = self.task_data, self.results
+        weighted = bool(self.params.weighted)
         check_device_args(self, tile, r.zero, r.a, r.b, r.selector, r.error)
         indices = td.device_indices.get(tile.device)
         if indices is None:

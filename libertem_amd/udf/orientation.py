@@ -26,13 +26,12 @@ On the device a tile goes through `ltmi_orient_match` (csrc/ltmi_orient.hip); on
 `match_polar` compute the same.  The normalised correlation index is correlation / polar_norm, by the caller.
 Not built: a pre-filter on the radial profile, sub-bin rotation refinement, a centre per frame, intensity transforms.
 """
-import hashlib
 import math
 
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.plans import PlanCache, array_digest, udf_device
 
 #: what `ltmi_orient_plan_create` takes (csrc/ltmi_orient.hip); MAX_POLAR_WORDS is `hip.orient_max_polar_words()`: the
 #: polar image shares the 160 KiB of LDS of a CU with 8 KiB of scores and 192 bytes of reduction scratch
@@ -40,7 +39,7 @@ MAX_BEST = 16
 MAX_PHI = 1024
 MAX_POLAR_WORDS = 38864
 NAMES = ('template', 'rotation', 'correlation', 'polar_norm')
-_PLANS = {}          # (device, h, w, n_best, digest of table and library) -> hip.OrientPlan
+_PLANS = PlanCache(8, owned=False)          # (device, h, w, n_best, digest of table and library) -> hip.OrientPlan
 
 
 def check_params(n_r, n_phi, n_best=1):
@@ -209,20 +208,12 @@ def rotation_angles(rotation, n_phi):
 def plan_for(udf, sig, tap_idx, tap_w, library, n_best):
     """the cached plan of a UDF's device, frame shape, sampling table, library and n_best"""
     from libertem_amd import hip
-    device = udf.meta.gpu_id if udf.meta.gpu_id is not None else 0
-    digest = hashlib.sha1()
-    for a in (tap_idx, tap_w) + tuple(library):
-        digest.update(a.tobytes())
-    key = (int(device), int(sig[0]), int(sig[1]), int(n_best), digest.hexdigest())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 8:
-            _PLANS.clear()          # (a plan goes with its last user: kept task instances may still hold one)
-        plan = _PLANS[key] = hip.OrientPlan(device, sig[0], sig[1], tap_idx, tap_w, library, n_best)
-    return plan
+    device = udf_device(udf)
+    key = (int(device), int(sig[0]), int(sig[1]), int(n_best), array_digest(tap_idx, tap_w, *library))
+    return _PLANS.get_or_make(key, lambda: hip.OrientPlan(device, sig[0], sig[1], tap_idx, tap_w, library, n_best))
 
 
-class OrientationMatchUDF(UDF):
+class OrientationMatchUDF(WholeFrameUDF):
     """
     Parameters
     ----------
@@ -241,21 +232,9 @@ class OrientationMatchUDF(UDF):
     raw score), 'polar_norm' (float32); slots from the number of templates on hold -1, -1 and NaN.
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, library, center, n_r, n_phi, n_best=1, r_min=1.0, delta_r=1.0):
         super().__init__(library=library, center=center, n_r=n_r, n_phi=n_phi, n_best=n_best, r_min=r_min,
                          delta_r=delta_r)
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
 
     def get_result_buffers(self):
         p = self.params
@@ -284,14 +263,6 @@ class OrientationMatchUDF(UDF):
             td.update(plan=plan_for(self, sig, tap_idx, tap_w, library, n_best))
         return td
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self._process_tile_numpy(tile)
-        else:
-            self._process_tile_hip(tile)
-
     def _process_tile_numpy(self, tile):
         td = self.task_data
         res = match_polar(polar_frames(np.asarray(tile), td.tap_idx, td.tap_w), td.library, td.n_best)
@@ -301,12 +272,9 @@ class OrientationMatchUDF(UDF):
     def _process_tile_hip(self, tile):
         r = self.results
         check_device_args(self, tile, r.template, r.rotation, r.correlation, r.polar_norm)
-        td = self.task_data
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"OrientationMatchUDF matches whole frames {td.sig}, got tiles of {tile.shape[1:]}")
-        td.plan.match(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, r.template.data_ptr(),
-                      r.rotation.data_ptr(), r.correlation.data_ptr(), r.polar_norm.data_ptr(),
-                      stream=self.meta.stream_ptr)
+        self.task_data.plan.match(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, r.template.data_ptr(),
+                                  r.rotation.data_ptr(), r.correlation.data_ptr(), r.polar_norm.data_ptr(),
+                                  stream=self.meta.stream_ptr)
 
 
 def run_orientation_match(ctx, dataset, library, center, n_r, n_phi, n_best=1, r_min=1.0, delta_r=1.0, roi=None):

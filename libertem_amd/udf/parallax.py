@@ -47,14 +47,14 @@ iteration is not built.
 """
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.correlation import CORR_WORKSPACE_BYTES
+from libertem_amd.common.hiparray import HipArray
 from libertem_amd.udf.device import quiet_floats
 from libertem_amd.udf.holography import signed_frequencies
-from libertem_amd.udf.ssb import SSBUDF, bf_pixels
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES, PlanCache
+from libertem_amd.udf.ssb import ScanPixelsUDF, _run_on_device, device_stream, disk_pixels
 
-_PLANS = {}          # (device, Ny, Nx, P, batch, max_shift) -> hip.ParallaxPlan; at most 2, closed on eviction and when
-                     # the executor of their device closes (`release_plans`)
+# (device, Ny, Nx, P, batch, max_shift) -> hip.ParallaxPlan; a plan holds the spectra and the workspace in HBM
+_PLANS = PlanCache(2, owned=True)
 
 RESULTS = ('shifts', 'matrix', 'offset', 'image', 'bright_field')
 
@@ -206,10 +206,8 @@ def parallax_bf(bf, nav_shape, sig, semiconv_pix, cy=None, cx=None, max_shift=4,
     nav = tuple(int(v) for v in nav_shape)
     check_scan(nav, p['max_shift'])
     ny, nx = nav
-    idx = bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
+    idx = disk_pixels(sig, p)
     bf = np.asarray(bf)
-    if idx.size == 0:
-        raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of {(p['cy'], p['cx'])}: P = 0")
     if bf.shape != (ny * nx, idx.size):
         raise ValueError(f"bf of shape {bf.shape} for a scan of {(ny, nx)} and {idx.size} bright-field pixels")
     offsets = pixel_offsets(sig, idx, p['cy'], p['cx'])
@@ -241,27 +239,18 @@ def plan_batch(nav_shape, n_idx):
 def _plan(device, nav_shape, n_idx, batch, max_shift):
     from libertem_amd import hip
     key = (int(device), nav_shape[0], nav_shape[1], int(n_idx), int(batch), int(max_shift))
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 2:
-            release_plans()         # (a plan holds the spectra and the workspace in HBM: it goes when it is evicted)
-        plan = _PLANS[key] = hip.ParallaxPlan(device, nav_shape[0], nav_shape[1], n_idx, batch, max_shift,
-                                              STORE_LIMIT_BYTES)
-    return plan
+    return _PLANS.get_or_make(key, lambda: hip.ParallaxPlan(device, nav_shape[0], nav_shape[1], n_idx, batch, max_shift,
+                                                            STORE_LIMIT_BYTES))
 
 
 def release_plans(device=None):
-    """Destroy the cached plans of `device` (None: of every device) and free their spectra and workspace.  The HIP
-    executor calls this when it closes; plans are used inside `get_results` only, so none is in use between two runs."""
-    for key in [k for k in _PLANS if device is None or k[0] == int(device)]:
-        _PLANS.pop(key).close()
+    """Destroy the cached plans of `device` (None: of every device) and free their spectra and workspace."""
+    _PLANS.release(device)
 
 
 def parallax_device(bf, nav_shape, offsets, max_shift, iterations=2, regularize=False, stream=None):
     """The results of a device-resident bf (HipArray (Ny Nx, P) float32) through the native plan; offsets: k - c of
     the P pixels (`pixel_offsets`).  -> the dict of `parallax_bf`"""
-    import torch
-    from libertem_amd.common.hiparray import HipArray
     ny, nx = nav_shape
     n_idx = len(offsets)
     if tuple(bf.shape) != (ny * nx, n_idx) or bf.dtype != np.float32:
@@ -269,11 +258,7 @@ def parallax_device(bf, nav_shape, offsets, max_shift, iterations=2, regularize=
     check_scan((ny, nx), max_shift)
     device = bf.device
     plan = _plan(device, (ny, nx), n_idx, plan_batch((ny, nx), n_idx), max_shift)
-    with torch.cuda.device(device):
-        if stream is None:
-            # the rows of bf were written on the executor's stream
-            torch.cuda.synchronize(device)
-            stream = torch.cuda.current_stream(device)
+    with device_stream(device, stream) as stream:
         plan.load(bf.data_ptr(), bf.ld, stream=stream)
         zeros = HipArray.zeros((n_idx, 2), np.float64, device)
         sh = HipArray.zeros((n_idx, 2), np.float64, device)
@@ -290,7 +275,7 @@ def parallax_device(bf, nav_shape, offsets, max_shift, iterations=2, regularize=
         return _results(sh.cpu(), offsets, (ny, nx), half_image, half_bf)
 
 
-class ParallaxUDF(SSBUDF):
+class ParallaxUDF(ScanPixelsUDF):
     """
     Parameters
     ----------
@@ -309,47 +294,29 @@ class ParallaxUDF(SSBUDF):
     the scan shape).  Buffer 'bf' (nav, on the device): the bright-field pixels of every frame, float32 (P).
     """
 
+    SINGLE_RESULTS = (('shifts', 'float64', ('P', 2)), ('matrix', 'float64', (2, 2)), ('offset', 'float64', (2,)),
+                      ('image', 'float32', 'nav'), ('bright_field', 'float32', 'nav'))
+
     def __init__(self, semiconv_pix, cy=None, cx=None, max_shift=4, iterations=2, regularize=False):
-        UDF.__init__(self, semiconv_pix=semiconv_pix, cy=cy, cx=cx, max_shift=max_shift, iterations=iterations,
-                     regularize=bool(regularize))
+        super().__init__(semiconv_pix=semiconv_pix, cy=cy, cx=cx, max_shift=max_shift, iterations=iterations,
+                         regularize=bool(regularize))
 
     def _geometry(self):
         """-> sig, nav, the checked parameters, the bright-field list; ValueError for what the operation cannot take"""
         pr = self.params
-        sig = tuple(int(s) for s in self.meta.dataset_shape.sig)
-        nav = tuple(int(s) for s in self.meta.dataset_shape.nav)
+        sig, nav = self._shapes()
         p = check_params(sig, pr.semiconv_pix, pr.cy, pr.cx, pr.max_shift, pr.iterations)
         check_scan(nav, p['max_shift'])
-        if self.meta.roi is not None:
-            raise ValueError("ParallaxUDF cannot take a roi: the transform over the scan needs the full rectangle")
-        idx = bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
-        if idx.size == 0:
-            raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of "
-                             f"{(p['cy'], p['cx'])}: P = 0")
-        return sig, nav, p, idx
+        self.check_scan_geometry(2)
+        return sig, nav, p, disk_pixels(sig, p)
 
-    def get_result_buffers(self):
-        _, nav, _, idx = self._geometry()
-        n_idx = int(idx.size)
-        shapes = {'shifts': ('float64', (n_idx, 2)), 'matrix': ('float64', (2, 2)), 'offset': ('float64', (2,)),
-                  'image': ('float32', nav), 'bright_field': ('float32', nav)}
-        bufs = {'bf': self.buffer(kind='nav', dtype='float32', extra_shape=(n_idx,), where='device')}
-        for name in RESULTS:
-            dtype, shape = shapes[name]
-            bufs[name] = self.buffer(kind='single', dtype=dtype, extra_shape=shape, use='result_only')
-        return bufs
+    def _reconstruct_device(self, bf, sig, nav, p, idx):
+        return parallax_device(bf, nav, pixel_offsets(sig, idx, p['cy'], p['cx']), p['max_shift'], p['iterations'],
+                               self.params.regularize)
 
-    def get_results(self):
-        from libertem_amd.common.hiparray import HipArray
-        sig, nav, p, idx = self._geometry()
-        bf = self.results.get_buffer('bf').result_array
-        if isinstance(bf, HipArray):
-            # a run with result_where='device': bf never left HBM
-            return parallax_device(bf.reshape((nav[0] * nav[1], idx.size)), nav,
-                                   pixel_offsets(sig, idx, p['cy'], p['cx']), p['max_shift'], p['iterations'],
-                                   self.params.regularize)
-        return parallax_bf(np.asarray(bf).reshape((nav[0] * nav[1], idx.size)), nav, sig, p['semiconv_pix'], p['cy'],
-                           p['cx'], p['max_shift'], p['iterations'], self.params.regularize)
+    def _reconstruct_host(self, bf, sig, nav, p, idx):
+        return parallax_bf(bf, nav, sig, p['semiconv_pix'], p['cy'], p['cx'], p['max_shift'], p['iterations'],
+                           self.params.regularize)
 
 
 def run_parallax(ctx, dataset, semiconv_pix, cy=None, cx=None, max_shift=4, iterations=2, regularize=False,
@@ -359,8 +326,4 @@ def run_parallax(ctx, dataset, semiconv_pix, cy=None, cx=None, max_shift=4, iter
     'image', 'bright_field' as host arrays, and with keep_bf 'bf', the HipArray (Ny, Nx, P)."""
     udf = ParallaxUDF(semiconv_pix=semiconv_pix, cy=cy, cx=cx, max_shift=max_shift, iterations=iterations,
                       regularize=regularize)
-    res = ctx.run_udf(dataset=dataset, udf=udf, result_where='device')
-    out = {name: np.asarray(res[name].data) for name in RESULTS}
-    if keep_bf:
-        out['bf'] = res['bf'].device_data
-    return out
+    return _run_on_device(ctx, dataset, udf, RESULTS, keep_bf)

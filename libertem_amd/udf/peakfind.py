@@ -24,9 +24,8 @@ this module.
 """
 import numpy as np
 
-from libertem_amd.udf.base import UDF
 from libertem_amd.udf.correlation import plan_for
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
 
 #: what `ltmi_correlate_find` takes (csrc/ltmi_peakfind.hip)
 MAX_PEAKS = 1024
@@ -155,7 +154,7 @@ def find_peaks(frame, template, num_peaks, min_distance, border=0, threshold_abs
     return centers[0, :int(n_found[0])].copy()
 
 
-class PeakFindUDF(UDF):
+class PeakFindUDF(WholeFrameUDF):
     """
     Parameters
     ----------
@@ -176,22 +175,10 @@ class PeakFindUDF(UDF):
     'peak_values' and 'peak_elevations' (float32, (N,)); slots from n_found on hold (-1, -1) and NaN.
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame get no result, on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, template, num_peaks, min_distance, border=0, threshold_abs=0.0, threshold_rel=0.0,
                  refine_radius=1):
         super().__init__(template=template, num_peaks=num_peaks, min_distance=min_distance, border=border,
                          threshold_abs=threshold_abs, threshold_rel=threshold_rel, refine_radius=refine_radius)
-
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the kernel converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
 
     def get_result_buffers(self):
         n = int(self.params.num_peaks)
@@ -226,14 +213,6 @@ class PeakFindUDF(UDF):
             td.update(plan=plan_for(self, sig, template))
         return td
 
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self._process_tile_numpy(tile)
-        else:
-            self._process_tile_hip(tile)
-
     def _process_tile_numpy(self, tile):
         td = self.task_data
         with quiet_floats():
@@ -246,8 +225,6 @@ class PeakFindUDF(UDF):
         r = self.results
         check_device_args(self, tile, r.n_found, r.centers, r.refineds, r.peak_values, r.peak_elevations)
         td = self.task_data
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"PeakFindUDF transforms whole frames {td.sig}, got tiles of {tile.shape[1:]}")
         td.plan.find_peaks(tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, *td.search,
                            r.n_found.data_ptr(), r.centers.data_ptr(), r.refineds.data_ptr(),
                            r.peak_values.data_ptr(), r.peak_elevations.data_ptr(), stream=self.meta.stream_ptr)

@@ -34,17 +34,23 @@ NumPy computes the definition in float64 / complex128 and casts at the end.  The
 (Ny, Nx) image is NumPy's in complex128 in both cases.
 Not part of this module: sub-pixel trotter masks, aberration correction, WDD and iterative ptychography.
 """
+import contextlib
+
 import numpy as np
 
-from libertem_amd.udf.base import UDF
-from libertem_amd.udf.correlation import CORR_WORKSPACE_BYTES
-from libertem_amd.udf.device import check_device_args, check_whole_frames, quiet_floats, runs_on_hip
+from libertem_amd.common.hiparray import HipArray
+from libertem_amd.udf.device import WholeFrameUDF, check_device_args, check_whole_frames, quiet_floats, runs_on_hip
 from libertem_amd.udf.holography import signed_frequencies
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES, PlanCache, udf_device
 
-_PLANS = {}          # (device, Ny, Nx, w, batch, cutoff, the geometry and the list as bytes) -> hip.SSBPlan; at most 2,
-                     # closed on eviction and when the executor of their device closes (`release_plans`)
+# (device, Ny, Nx, w, batch, cutoff, the geometry and the list as bytes) -> hip.SSBPlan; a plan holds up to the
+# workspace budget of HBM
+_PLANS = PlanCache(2, owned=True)
 
-RESULTS = ('fourier', 'complex', 'phase', 'amplitude')
+#: (name, dtype, extra shape) of the results of SSBUDF and WDDUDF; 'nav': the scan shape
+IMAGE_RESULTS = (('fourier', 'complex64', 'nav'), ('complex', 'complex64', 'nav'), ('phase', 'float32', 'nav'),
+                 ('amplitude', 'float32', 'nav'))
+RESULTS = tuple(name for name, _, _ in IMAGE_RESULTS)
 
 
 def wavelength(kilovolts):
@@ -92,6 +98,15 @@ def bf_pixels(sig, semiconv_pix, cy, cx):
     return np.flatnonzero(inside.reshape(-1)).astype(np.int32)
 
 
+def disk_pixels(sig, p):
+    """`bf_pixels` of the checked parameters p; ValueError for an empty disk"""
+    idx = bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
+    if idx.size == 0:
+        raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of {(p['cy'], p['cx'])}: "
+                         f"P = 0")
+    return idx
+
+
 def _shifts(p, nav_shape, iy):
     """d of the Qs (iy, 0 .. Nx - 1) -> (d_y, d_x), float64 (Nx) each"""
     ny, nx = nav_shape
@@ -133,10 +148,13 @@ def trotter_masks(sig, q_index, nav_shape, **params):
     return out[0].reshape(h, w), out[1].reshape(h, w)
 
 
-def _images(fourier):
-    """fourier (complex64 or complex128, unshifted) -> the four results in their result dtypes"""
+def _images(fourier, scale=1.0):
+    """fourier (complex64 or complex128, unshifted) -> the four results in their result dtypes; complex =
+    scale ifft2(fourier)"""
     with quiet_floats():
         cplx = np.fft.ifft2(np.asarray(fourier).astype(np.complex128))
+        if scale != 1.0:
+            cplx = cplx * scale         # (not by 1: a complex product turns -0 into +0, which `angle` tells apart)
         return {'fourier': np.asarray(fourier).astype(np.complex64), 'complex': cplx.astype(np.complex64),
                 'phase': np.angle(cplx).astype(np.float32), 'amplitude': np.abs(cplx).astype(np.float32)}
 
@@ -149,10 +167,8 @@ def reconstruct_bf(bf, nav_shape, sig, lamb, dpix, semiconv, semiconv_pix, cy=No
     p = check_params(sig, lamb, dpix, semiconv, semiconv_pix, cy, cx, transformation, cutoff)
     ny, nx = (int(v) for v in nav_shape)
     w = int(sig[1])
-    idx = bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
+    idx = disk_pixels(sig, p)
     bf = np.asarray(bf)
-    if idx.size == 0:
-        raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of {(p['cy'], p['cx'])}")
     if bf.shape != (ny * nx, idx.size):
         raise ValueError(f"bf of shape {bf.shape} for a scan of {(ny, nx)} and {idx.size} bright-field pixels")
     y, x = (idx // w).astype(np.float64), (idx % w).astype(np.float64)
@@ -176,19 +192,13 @@ def _plan(device, nav_shape, sig_w, idx, batch, p):
     from libertem_amd import hip
     geom = hip.ssb_geometry(p['lamb'], (p['dy'], p['dx']), p['semiconv'], p['semiconv_pix'], p['cy'], p['cx'], p['t'])
     key = (int(device), nav_shape[0], nav_shape[1], int(sig_w), int(batch), p['cutoff'], geom.tobytes(), idx.tobytes())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 2:
-            release_plans()         # (a plan holds up to the workspace budget of HBM: it goes when it is evicted)
-        plan = _PLANS[key] = hip.SSBPlan(device, nav_shape[0], nav_shape[1], sig_w, idx, batch, geom, p['cutoff'])
-    return plan
+    return _PLANS.get_or_make(key, lambda: hip.SSBPlan(device, nav_shape[0], nav_shape[1], sig_w, idx, batch, geom,
+                                                       p['cutoff']))
 
 
 def release_plans(device=None):
-    """Destroy the cached plans of `device` (None: of every device) and free their workspace.  The HIP executor calls
-    this when it closes; plans are used inside `get_results` only, so none is in use between two runs."""
-    for key in [k for k in _PLANS if device is None or k[0] == int(device)]:
-        _PLANS.pop(key).close()
+    """Destroy the cached plans of `device` (None: of every device) and free their workspace."""
+    _PLANS.release(device)
 
 
 def plan_batch(nav_shape, n_idx):
@@ -201,28 +211,115 @@ def plan_batch(nav_shape, n_idx):
     return int(max(1, min(budget // per_pixel, n_idx)))
 
 
-def reconstruct_device(bf, nav_shape, sig_w, idx, p, stream=None):
-    """`fourier` of a device-resident bf (HipArray (Ny Nx, P) float32) through the native plan -> complex64 (Ny, Nx)
-    on the host"""
+@contextlib.contextmanager
+def device_stream(device, stream=None):
+    """`device` as torch's current one, and the stream to launch on: `stream`, or -- after everything enqueued on the
+    device has finished: the rows of bf were written on the executor's stream -- torch's current stream"""
     import torch
-    from libertem_amd.common.hiparray import HipArray
-    ny, nx = nav_shape
-    if tuple(bf.shape) != (ny * nx, idx.size) or bf.dtype != np.float32:
-        raise ValueError(f"bf {bf.shape} {bf.dtype} for a scan of {(ny, nx)} and {idx.size} bright-field pixels")
-    device = bf.device
-    plan = _plan(device, (ny, nx), sig_w, idx, plan_batch((ny, nx), idx.size), p)
     with torch.cuda.device(device):
         if stream is None:
-            # the rows of bf were written on the executor's stream
             torch.cuda.synchronize(device)
             stream = torch.cuda.current_stream(device)
-        fourier = HipArray.empty((ny, nx), np.complex64, device)
+        yield stream
+
+
+def plan_fourier(plan, bf, nav_shape, stream=None):
+    """`plan.reconstruct` (an SSBPlan's or a WDDPlan's) of a device-resident bf -> complex64 (Ny, Nx) on the host"""
+    with device_stream(bf.device, stream) as stream:
+        fourier = HipArray.empty(tuple(nav_shape), np.complex64, bf.device)
         plan.reconstruct(bf.data_ptr(), bf.ld, fourier.data_ptr(), stream=stream)
         stream.synchronize()
         return fourier.cpu()
 
 
-class SSBUDF(UDF):
+def reconstruct_device(bf, nav_shape, sig_w, idx, p, stream=None):
+    """`fourier` of a device-resident bf (HipArray (Ny Nx, P) float32) through the native plan -> complex64 (Ny, Nx)
+    on the host"""
+    ny, nx = nav_shape
+    if tuple(bf.shape) != (ny * nx, idx.size) or bf.dtype != np.float32:
+        raise ValueError(f"bf {bf.shape} {bf.dtype} for a scan of {(ny, nx)} and {idx.size} bright-field pixels")
+    plan = _plan(bf.device, (ny, nx), sig_w, idx, plan_batch((ny, nx), idx.size), p)
+    return plan_fourier(plan, bf, (ny, nx), stream)
+
+
+class ScanPixelsUDF(WholeFrameUDF):
+    """
+    What the UDFs share that reconstruct one image from a list of detector pixels of every frame of a 2D scan.  The
+    listed pixels are gathered into the buffer 'bf' (nav, on the device, float32 (len(list),)), the only pass over the
+    frames; `get_results` reconstructs from the whole of it.  Positions a sync_offset leaves without a frame keep zero
+    rows in 'bf', on the device as on the host.
+
+    A subclass gives `_geometry() -> sig, nav, p, idx` (the frame and scan shapes, its checked parameters, the pixel
+    list as int32 frame indices), `_reconstruct_device(bf, sig, nav, p, idx)` for a HipArray bf (Ny Nx, len(idx)) and
+    `_reconstruct_host` for a NumPy one, both -> the dict of its results, and SINGLE_RESULTS where they are not the
+    four images.
+    """
+
+    #: (name, dtype, extra shape) of the results; 'nav': the scan shape, 'P' in a shape: len(idx)
+    SINGLE_RESULTS = IMAGE_RESULTS
+
+    def _shapes(self):
+        shape = self.meta.dataset_shape
+        return tuple(int(s) for s in shape.sig), tuple(int(s) for s in shape.nav)
+
+    def check_scan_geometry(self, min_positions):
+        """ValueError for a scan that is not 2D or holds fewer than `min_positions` positions, and for a roi"""
+        name, nav = type(self).__name__, self._shapes()[1]
+        if len(nav) != 2 or nav[0] * nav[1] < min_positions:
+            raise ValueError(f"{name} needs a 2D scan of at least {min_positions} positions, not {nav}")
+        if self.meta.roi is not None:
+            raise ValueError(f"{name} cannot take a roi: the transform over the scan needs the full rectangle")
+
+    def get_result_buffers(self):
+        _, nav, _, idx = self._geometry()
+        n_idx = int(idx.size)
+        bufs = {'bf': self.buffer(kind='nav', dtype='float32', extra_shape=(n_idx,), where='device')}
+        for name, dtype, shape in self.SINGLE_RESULTS:
+            shape = nav if shape == 'nav' else tuple(n_idx if s == 'P' else s for s in shape)
+            bufs[name] = self.buffer(kind='single', dtype=dtype, extra_shape=shape, use='result_only')
+        return bufs
+
+    def get_dist_merge(self):
+        return {'bf': 'disjoint'}
+
+    def get_write_once_buffers(self):
+        """whole-frame tiles: every row of 'bf' is written by one gather call (see SumSigUDF.get_write_once_buffers),
+        so a partition's rows may go straight into the buffer of the whole scan"""
+        ts = self.meta.tiling_scheme if self.meta is not None else None
+        if self.meta is not None and self.meta.array_backend == self.BACKEND_NUMPY:
+            return ()
+        if ts is None or len(ts) != 1 or getattr(self.meta, 'sig_sliced_tiles', False):
+            return ()
+        return ('bf',)
+
+    def get_task_data(self):
+        check_whole_frames(self)
+        sig, _, _, idx = self._geometry()
+        td = {'sig': sig, 'idx': idx}
+        if runs_on_hip(self):
+            td.update(idx_dev=HipArray.from_numpy(idx, udf_device(self)))
+        return td
+
+    def _process_tile_numpy(self, tile):
+        self.results.bf[:] = np.asarray(tile).reshape((tile.shape[0], -1))[:, self.task_data.idx]
+
+    def _process_tile_hip(self, tile):
+        from libertem_amd import hip
+        td, bf = self.task_data, self.results.bf
+        check_device_args(self, tile, bf)
+        hip.ssb_gather(tile.device, tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, td.sig[0] * td.sig[1],
+                       td.idx_dev.data_ptr(), td.idx.size, bf.data_ptr(), bf.ld, stream=self.meta.stream_ptr)
+
+    def get_results(self):
+        sig, nav, p, idx = self._geometry()
+        bf = self.results.get_buffer('bf').result_array
+        if isinstance(bf, HipArray):
+            # a run with result_where='device': bf never left HBM
+            return self._reconstruct_device(bf.reshape((nav[0] * nav[1], idx.size)), sig, nav, p, idx)
+        return self._reconstruct_host(np.asarray(bf).reshape((nav[0] * nav[1], idx.size)), sig, nav, p, idx)
+
+
+class SSBUDF(ScanPixelsUDF):
     """
     Parameters
     ----------
@@ -246,97 +343,36 @@ class SSBUDF(UDF):
     Buffer 'bf' (nav, on the device): the bright-field pixels of every frame, float32 (P).
     """
 
-    REUSE_TASK_INSTANCES = True
-    #: positions a sync_offset leaves without a frame keep zero rows in 'bf', on the device as on the host
-    VALID_FRAMES_ONLY = True
-    WHOLE_FRAME_TILES = True
-
     def __init__(self, lamb, dpix, semiconv, semiconv_pix, cy=None, cx=None, transformation=None, cutoff=1):
         super().__init__(lamb=lamb, dpix=dpix, semiconv=semiconv, semiconv_pix=semiconv_pix, cy=cy, cx=cx,
                          transformation=transformation, cutoff=cutoff)
 
-    def get_preferred_input_dtype(self):
-        # the frames as stored: the gather converts in registers
-        return self.USE_NATIVE_DTYPE
-
-    def get_backends(self):
-        return (self.BACKEND_HIP, self.BACKEND_NUMPY)
-
     def _geometry(self):
         """-> sig, nav, the checked parameters, the bright-field list; ValueError for what the operation cannot take"""
         pr = self.params
-        sig = tuple(int(s) for s in self.meta.dataset_shape.sig)
-        nav = tuple(int(s) for s in self.meta.dataset_shape.nav)
+        sig, nav = self._shapes()
         p = check_params(sig, pr.lamb, pr.dpix, pr.semiconv, pr.semiconv_pix, pr.cy, pr.cx, pr.transformation,
                          pr.cutoff)
-        if len(nav) != 2 or nav[0] * nav[1] < 2:
-            raise ValueError(f"SSBUDF needs a 2D scan of at least two positions, not {nav}")
-        if self.meta.roi is not None:
-            raise ValueError("SSBUDF cannot take a roi: the transform over the scan needs the full rectangle")
-        idx = bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
-        if idx.size == 0:
-            raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of "
-                             f"{(p['cy'], p['cx'])}: P = 0")
-        return sig, nav, p, idx
+        self.check_scan_geometry(2)
+        return sig, nav, p, disk_pixels(sig, p)
 
-    def get_result_buffers(self):
-        _, nav, _, idx = self._geometry()
-        bufs = {'bf': self.buffer(kind='nav', dtype='float32', extra_shape=(int(idx.size),), where='device')}
-        for name in RESULTS:
-            dtype = 'complex64' if name in ('fourier', 'complex') else 'float32'
-            bufs[name] = self.buffer(kind='single', dtype=dtype, extra_shape=nav, use='result_only')
-        return bufs
+    def _reconstruct_device(self, bf, sig, nav, p, idx):
+        return _images(reconstruct_device(bf, nav, sig[1], idx, p))
 
-    def get_dist_merge(self):
-        return {'bf': 'disjoint'}
+    def _reconstruct_host(self, bf, sig, nav, p, idx):
+        pr = self.params
+        return reconstruct_bf(bf, nav, sig, pr.lamb, pr.dpix, pr.semiconv, pr.semiconv_pix, pr.cy, pr.cx,
+                              pr.transformation, pr.cutoff)
 
-    def get_write_once_buffers(self):
-        """whole-frame tiles: every row of 'bf' is written by one gather call (see SumSigUDF.get_write_once_buffers),
-        so a partition's rows may go straight into the buffer of the whole scan"""
-        ts = self.meta.tiling_scheme if self.meta is not None else None
-        if self.meta is not None and self.meta.array_backend == self.BACKEND_NUMPY:
-            return ()
-        if ts is None or len(ts) != 1 or getattr(self.meta, 'sig_sliced_tiles', False):
-            return ()
-        return ('bf',)
 
-    def get_task_data(self):
-        check_whole_frames(self)
-        sig, nav, p, idx = self._geometry()
-        td = {'sig': sig, 'idx': idx}
-        if runs_on_hip(self):
-            from libertem_amd.common.hiparray import HipArray
-            device = self.meta.gpu_id if self.meta.gpu_id is not None else 0
-            td.update(idx_dev=HipArray.from_numpy(idx, device))
-        return td
-
-    def process_tile(self, tile):
-        if tile.shape[0] == 0:
-            return
-        td = self.task_data
-        if self.meta.array_backend == self.BACKEND_NUMPY:
-            self.results.bf[:] = np.asarray(tile).reshape((tile.shape[0], -1))[:, td.idx]
-            return
-        from libertem_amd import hip
-        bf = self.results.bf
-        check_device_args(self, tile, bf)
-        if tuple(tile.shape[1:]) != td.sig:
-            raise ValueError(f"SSBUDF gathers from whole frames {td.sig}, got tiles of {tile.shape[1:]}")
-        hip.ssb_gather(tile.device, tile.data_ptr(), tile.dtype, tile.shape[0], tile.ld, td.sig[0] * td.sig[1],
-                       td.idx_dev.data_ptr(), td.idx.size, bf.data_ptr(), bf.ld, stream=self.meta.stream_ptr)
-
-    def get_results(self):
-        from libertem_amd.common.hiparray import HipArray
-        sig, nav, p, idx = self._geometry()
-        bf = self.results.get_buffer('bf').result_array
-        if isinstance(bf, HipArray):
-            # a run with result_where='device': bf never left HBM
-            out = _images(reconstruct_device(bf.reshape((nav[0] * nav[1], idx.size)), nav, sig[1], idx, p))
-        else:
-            pr = self.params
-            out = reconstruct_bf(np.asarray(bf).reshape((nav[0] * nav[1], idx.size)), nav, sig, pr.lamb, pr.dpix,
-                                 pr.semiconv, pr.semiconv_pix, pr.cy, pr.cx, pr.transformation, pr.cutoff)
-        return out
+def _run_on_device(ctx, dataset, udf, names, keep_bf):
+    """`udf` on a HIP context with 'bf' left on the device -> dict of the results `names` as host arrays, and with
+    keep_bf 'bf', the HipArray"""
+    res = ctx.run_udf(dataset=dataset, udf=udf, result_where='device')
+    out = {name: np.asarray(res[name].data) for name in names}
+    if keep_bf:
+        out['bf'] = res['bf'].device_data
+    return out
 
 
 def run_ssb(ctx, dataset, lamb, dpix, semiconv, semiconv_pix, cy=None, cx=None, transformation=None, cutoff=1,
@@ -346,8 +382,4 @@ def run_ssb(ctx, dataset, lamb, dpix, semiconv, semiconv_pix, cy=None, cx=None, 
     'amplitude' as host arrays (Ny, Nx), and with keep_bf 'bf', the HipArray (Ny, Nx, P)."""
     udf = SSBUDF(lamb=lamb, dpix=dpix, semiconv=semiconv, semiconv_pix=semiconv_pix, cy=cy, cx=cx,
                  transformation=transformation, cutoff=cutoff)
-    res = ctx.run_udf(dataset=dataset, udf=udf, result_where='device')
-    out = {name: np.asarray(res[name].data) for name in RESULTS}
-    if keep_bf:
-        out['bf'] = res['bf'].device_data
-    return out
+    return _run_on_device(ctx, dataset, udf, RESULTS, keep_bf)

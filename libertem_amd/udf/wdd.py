@@ -36,12 +36,12 @@ the probe, the inverse transform on the device, iterative ptychography.
 import numpy as np
 
 from libertem_amd.udf import ssb
-from libertem_amd.udf.base import UDF
 from libertem_amd.udf.device import quiet_floats
-from libertem_amd.udf.ssb import RESULTS, SSBUDF
+from libertem_amd.udf.plans import PlanCache
 
-_PLANS = {}          # (device, Ny, Nx, batch, epsilon, the geometry and the window as bytes) -> hip.WDDPlan; at most 2,
-                     # closed on eviction and when the executor of their device closes (`release_plans`)
+# (device, Ny, Nx, batch, epsilon, the geometry and the window as bytes) -> hip.WDDPlan; a plan holds F and the
+# workspace in HBM
+_PLANS = PlanCache(2, owned=True)
 
 
 def check_params(sig, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.01, cy=None, cx=None,
@@ -51,23 +51,19 @@ def check_params(sig, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.01, 
     p = ssb.check_params(sig, lamb, dpix, semiconv, semiconv_pix, cy, cx, transformation)
     del p['cutoff']
     h, w = (int(s) for s in sig)
-    by, bx = _window_shape(window)
+    y0, x0, by, bx = _window_at(window, p['cy'], p['cx'])
     try:
         eps = float(epsilon)
     except (TypeError, ValueError):
         raise ValueError(f"epsilon {epsilon!r} must be a number")
     if not (np.isfinite(eps) and eps > 0):
         raise ValueError(f"epsilon {epsilon!r} must be positive and finite")
-    y0, x0 = int(np.floor(p['cy'])) - by // 2, int(np.floor(p['cx'])) - bx // 2
     if y0 < 0 or y0 + by > h:
         raise ValueError(f"window rows [{y0}, {y0 + by}) (By = {by} around cy = {p['cy']}) leave the frame of {h} rows")
     if x0 < 0 or x0 + bx > w:
         raise ValueError(f"window columns [{x0}, {x0 + bx}) (Bx = {bx} around cx = {p['cx']}) leave the frame of "
                          f"{w} columns")
-    disk = ssb.bf_pixels(sig, p['semiconv_pix'], p['cy'], p['cx'])
-    if disk.size == 0:
-        raise ValueError(f"no detector pixel lies within semiconv_pix {p['semiconv_pix']} of {(p['cy'], p['cx'])}: "
-                         f"P = 0")
+    disk = ssb.disk_pixels(sig, p)
     y, x = disk // w, disk % w
     outside = (y < y0) | (y >= y0 + by) | (x < x0) | (x >= x0 + bx)
     if outside.any():
@@ -82,21 +78,21 @@ def window_pixels(sig, window, cy=None, cx=None):
     [x0, x0 + Bx) with y0 = floor(cy) - By // 2, x0 = floor(cx) - Bx // 2 -> int32 (By Bx); ValueError for a window
     that leaves the frame"""
     h, w = (int(s) for s in sig)
-    by, bx = _window_shape(window)
     cy = h / 2 if cy is None else float(cy)
     cx = w / 2 if cx is None else float(cx)
-    y0, x0 = int(np.floor(cy)) - by // 2, int(np.floor(cx)) - bx // 2
-    return _window_list((h, w), (y0, x0, by, bx))
+    return _window_list((h, w), _window_at(window, cy, cx))
 
 
-def _window_shape(window):
+def _window_at(window, cy, cx):
+    """-> (y0, x0, By, Bx) of the window (By, Bx), or of one integer for both, around the centre (cy, cx)"""
     try:
         by, bx = (window, window) if np.ndim(window) == 0 else window
         if int(by) != by or int(bx) != bx or int(by) < 1 or int(bx) < 1:
             raise ValueError
     except (TypeError, ValueError):
         raise ValueError(f"window {window!r} must be an integer or (By, Bx), each >= 1")
-    return int(by), int(bx)
+    by, bx = int(by), int(bx)
+    return int(np.floor(cy)) - by // 2, int(np.floor(cx)) - bx // 2, by, bx
 
 
 def _window_list(sig, window):
@@ -138,15 +134,6 @@ def wdd_filter(sig, q_index, nav_shape, **params):
     return _filters(p, (ny, nx), iy)[ix]
 
 
-def _images(fourier):
-    """fourier (complex64 or complex128, unshifted) -> the four results in their result dtypes"""
-    with quiet_floats():
-        f = np.asarray(fourier).astype(np.complex128)
-        cplx = np.fft.ifft2(f) * f.size
-        return {'fourier': np.asarray(fourier).astype(np.complex64), 'complex': cplx.astype(np.complex64),
-                'phase': np.angle(cplx).astype(np.float32), 'amplitude': np.abs(cplx).astype(np.float32)}
-
-
 def reconstruct_window(bf, nav_shape, sig, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.01, cy=None, cx=None,
                        transformation=None):
     """The definition in NumPy from bf (Ny Nx, By Bx), the window pixels `window_pixels(sig, window, cy, cx)` of every
@@ -167,7 +154,7 @@ def reconstruct_window(bf, nav_shape, sig, lamb, dpix, semiconv, semiconv_pix, w
             s[iy] = (g[:, iy, :].T * f).sum(axis=1) / (by * bx)
         mirrored = s[(-np.arange(ny)) % ny][:, (-np.arange(nx)) % nx]
         fourier = np.conj(mirrored) / np.abs(s[0, 0])
-    return _images(fourier)
+    return ssb._images(fourier, fourier.size)
 
 
 def _plan(device, nav_shape, batch, p):
@@ -175,44 +162,27 @@ def _plan(device, nav_shape, batch, p):
     geom = hip.ssb_geometry(p['lamb'], (p['dy'], p['dx']), p['semiconv'], p['semiconv_pix'], p['cy'], p['cx'], p['t'])
     window = np.asarray(p['window'], dtype=np.int32)
     key = (int(device), nav_shape[0], nav_shape[1], int(batch), p['epsilon'], geom.tobytes(), window.tobytes())
-    plan = _PLANS.get(key)
-    if plan is None:
-        if len(_PLANS) >= 2:
-            release_plans()         # (a plan holds F and the workspace in HBM: it goes when it is evicted)
-        plan = _PLANS[key] = hip.WDDPlan(device, nav_shape[0], nav_shape[1], window, batch, geom, p['epsilon'])
-    return plan
+    return _PLANS.get_or_make(key, lambda: hip.WDDPlan(device, nav_shape[0], nav_shape[1], window, batch, geom,
+                                                       p['epsilon']))
 
 
 def release_plans(device=None):
-    """Destroy the cached plans of `device` (None: of every device) and free their filters and workspace.  The HIP
-    executor calls this when it closes; plans are used inside `get_results` only, so none is in use between two runs."""
-    for key in [k for k in _PLANS if device is None or k[0] == int(device)]:
-        _PLANS.pop(key).close()
+    """Destroy the cached plans of `device` (None: of every device) and free their filters and workspace."""
+    _PLANS.release(device)
 
 
 def reconstruct_device(bf, nav_shape, p, stream=None):
     """`fourier` of a device-resident bf (HipArray (Ny Nx, By Bx) float32) through the native plan -> complex64
     (Ny, Nx) on the host"""
-    import torch
-    from libertem_amd.common.hiparray import HipArray
     ny, nx = nav_shape
     n_window = p['window'][2] * p['window'][3]
     if tuple(bf.shape) != (ny * nx, n_window) or bf.dtype != np.float32:
         raise ValueError(f"bf {bf.shape} {bf.dtype} for a scan of {(ny, nx)} and {n_window} window pixels")
-    device = bf.device
-    plan = _plan(device, (ny, nx), ssb.plan_batch((ny, nx), n_window), p)
-    with torch.cuda.device(device):
-        if stream is None:
-            # the rows of bf were written on the executor's stream
-            torch.cuda.synchronize(device)
-            stream = torch.cuda.current_stream(device)
-        fourier = HipArray.empty((ny, nx), np.complex64, device)
-        plan.reconstruct(bf.data_ptr(), bf.ld, fourier.data_ptr(), stream=stream)
-        stream.synchronize()
-        return fourier.cpu()
+    plan = _plan(bf.device, (ny, nx), ssb.plan_batch((ny, nx), n_window), p)
+    return ssb.plan_fourier(plan, bf, (ny, nx), stream)
 
 
-class WDDUDF(SSBUDF):
+class WDDUDF(ssb.ScanPixelsUDF):
     """
     Parameters
     ----------
@@ -229,33 +199,26 @@ class WDDUDF(SSBUDF):
 
     def __init__(self, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.01, cy=None, cx=None,
                  transformation=None):
-        UDF.__init__(self, lamb=lamb, dpix=dpix, semiconv=semiconv, semiconv_pix=semiconv_pix, window=window,
-                     epsilon=epsilon, cy=cy, cx=cx, transformation=transformation)
+        super().__init__(lamb=lamb, dpix=dpix, semiconv=semiconv, semiconv_pix=semiconv_pix, window=window,
+                         epsilon=epsilon, cy=cy, cx=cx, transformation=transformation)
 
     def _geometry(self):
         """-> sig, nav, the checked parameters, the window's list; ValueError for what the operation cannot take"""
         pr = self.params
-        sig = tuple(int(s) for s in self.meta.dataset_shape.sig)
-        nav = tuple(int(s) for s in self.meta.dataset_shape.nav)
+        sig, nav = self._shapes()
         p = check_params(sig, pr.lamb, pr.dpix, pr.semiconv, pr.semiconv_pix, pr.window, pr.epsilon, pr.cy, pr.cx,
                          pr.transformation)
-        if len(nav) != 2 or nav[0] * nav[1] < 2:
-            raise ValueError(f"WDDUDF needs a 2D scan of at least two positions, not {nav}")
-        if self.meta.roi is not None:
-            raise ValueError("WDDUDF cannot take a roi: the transform over the scan needs the full rectangle")
+        self.check_scan_geometry(2)
         return sig, nav, p, _window_list(sig, p['window'])
 
-    def get_results(self):
-        from libertem_amd.common.hiparray import HipArray
-        sig, nav, p, idx = self._geometry()
-        bf = self.results.get_buffer('bf').result_array
-        if isinstance(bf, HipArray):
-            # a run with result_where='device': bf never left HBM
-            return _images(reconstruct_device(bf.reshape((nav[0] * nav[1], idx.size)), nav, p))
+    def _reconstruct_device(self, bf, sig, nav, p, idx):
+        fourier = reconstruct_device(bf, nav, p)
+        return ssb._images(fourier, fourier.size)
+
+    def _reconstruct_host(self, bf, sig, nav, p, idx):
         pr = self.params
-        return reconstruct_window(np.asarray(bf).reshape((nav[0] * nav[1], idx.size)), nav, sig, pr.lamb, pr.dpix,
-                                  pr.semiconv, pr.semiconv_pix, pr.window, pr.epsilon, pr.cy, pr.cx,
-                                  pr.transformation)
+        return reconstruct_window(bf, nav, sig, pr.lamb, pr.dpix, pr.semiconv, pr.semiconv_pix, pr.window, pr.epsilon,
+                                  pr.cy, pr.cx, pr.transformation)
 
 
 def run_wdd(ctx, dataset, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.01, cy=None, cx=None,
@@ -265,8 +228,4 @@ def run_wdd(ctx, dataset, lamb, dpix, semiconv, semiconv_pix, window, epsilon=0.
     as host arrays (Ny, Nx), and with keep_bf 'bf', the HipArray (Ny, Nx, By Bx)."""
     udf = WDDUDF(lamb=lamb, dpix=dpix, semiconv=semiconv, semiconv_pix=semiconv_pix, window=window, epsilon=epsilon,
                  cy=cy, cx=cx, transformation=transformation)
-    res = ctx.run_udf(dataset=dataset, udf=udf, result_where='device')
-    out = {name: np.asarray(res[name].data) for name in RESULTS}
-    if keep_bf:
-        out['bf'] = res['bf'].device_data
-    return out
+    return ssb._run_on_device(ctx, dataset, udf, ssb.RESULTS, keep_bf)

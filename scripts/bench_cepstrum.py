@@ -17,7 +17,7 @@ import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from libertem_amd import hip
 from libertem_amd.api import Context
-from libertem_amd.udf.correlation import CORR_WORKSPACE_BYTES
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES
 from libertem_amd.udf.cepstrum import CepstrumUDF, hann_window
 from libertem_amd.udf.holography import disk_aperture
 from libertem_amd.utils.generate import strained_lattice_scan

@@ -17,7 +17,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from libertem_amd import hip, masks
 from libertem_amd.api import Context
 from libertem_amd.executor.inline import InlineJobExecutor
-from libertem_amd.udf.correlation import CorrelationUDF, CORR_WORKSPACE_BYTES
+from libertem_amd.udf.correlation import CorrelationUDF
+from libertem_amd.udf.plans import CORR_WORKSPACE_BYTES
 
 PEAK = 8000.                # GB/s
 quick = '--quick' in sys.argv
